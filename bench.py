@@ -23,6 +23,16 @@ counts 60/39 s; value = (windows processed by all ranks x 60/39) / max-over-
 ranks wall time.  Multi-GPU: one process per GPU (torchrun, or ``--gpus N``
 which spawns the N ranks itself), each with its own clips (weak scaling); the
 only collective is the final RCCL all-gather of per-track results (§8e).
+
+A plain run (no ``--full``) sets up, lets the clocks settle (a quarter of a
+second of untimed steps), warms up, times the K steps and prints the result
+line: nothing else.  ``--full`` adds everything above that is not
+the headline figure -- the per-stage calibration and rooflines, the parity
+gate against the CPU oracle, the secondary measurements and the CPU baseline
+-- and writes the full record beside the run.  ``--dump-outputs DIR`` writes
+what the last timed step computed (log-mel, logits, probabilities, track
+means) as DIR/<name>.npy; inputs and models are seeded, so two builds run with
+the same arguments can be compared array for array.
 """
 from __future__ import annotations
 
@@ -93,6 +103,14 @@ def parse(argv=None):
                     help="ranks; without torchrun's env, bench.py spawns one process per GPU itself")
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="--config 2: besides the headline, the per-stage calibration and rooflines, the parity "
+                         "gate against the CPU oracle, the secondaries (--secondary) and the CPU baseline "
+                         "(--cpu-seconds), and the full record written beside the run; off: set up, warm up, "
+                         "time --steps steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed as DIR/<name>.npy "
+                         "(float32; --config 2: logmel, logits, probs, track_mean; --config 3: track_scores)")
     ap.add_argument("--model", default="model1", choices=sorted(WORKLOADS),
                     help="model1: the build-defined sparrow-style CNN (headline); effnetv2: an EfficientNetV2-B0-"
                          "shaped graph on 3-channel log-mel (the efficientnet route)")
@@ -127,7 +145,10 @@ def parse(argv=None):
                          "Python -- decode, tracks, JSON -- scale with processes, not threads); ranks sharing "
                          "a GPU gather over gloo.  --config 2: ranks sharing one GPU over gloo (rehearses the "
                          "N-rank path -- per-rank parity gate, max-over-ranks time, record gather -- on one GPU)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.dump_outputs and args.config == 4:
+        ap.error("--dump-outputs: --config 4 returns JSON documents, not arrays (use --config 2 or 3)")
+    return args
 
 
 def fe_settings(model="model1"):
@@ -375,6 +396,16 @@ class Step:
         self.model.forward(self.logmel, self.logits, self.probs, workspace=self.m_ws)
         track_mean(self.probs[None], self.wb, self.wc, out=self.tmean)
 
+    def outputs(self):
+        """What the last step computed, as a caller of the path receives it:
+        {name: device tensor}, the buffers of that step's lane."""
+        k = self.k - 1
+        if self.lanes is not None:
+            L = self.lanes[k % len(self.lanes)]
+            return {"logmel": L["logmel"], "logits": L["logits"], "probs": L["probs"], "track_mean": L["tmean"]}
+        logmel = self.lm2[k % 2] if self.pipeline else self.logmel
+        return {"logmel": logmel, "logits": self.logits, "probs": self.probs, "track_mean": self.tmean}
+
     def launches(self):
         return [(self.fe, i) for i in range(self.fe.n_stages())] + \
                [(self.model, i) for i in range(self.model.n_stages())]
@@ -393,6 +424,47 @@ def timed(step, steps, warmup, world):
     if world > 1:
         dist.barrier()
     return time.perf_counter() - t0
+
+
+DUMP_LIMIT = 64 * 10 ** 6  # bytes, all arrays of one --dump-outputs together
+
+
+def dump_outputs(directory, arrays, rank=0):
+    """--dump-outputs: {name: tensor or ndarray} -> DIR/<name>.npy (rank r > 0:
+    <name>_rank<r>.npy), float32 (float64 stays float64).  Every array gets an
+    equal share of DUMP_LIMIT; one that would not fit is written as a fixed
+    sample of its elements in flat (C) order -- indices drawn once from
+    numpy's default_rng(0), sorted -- so two runs sample the same places."""
+    out = Path(directory)
+    out.mkdir(parents=True, exist_ok=True)
+    share = DUMP_LIMIT // max(len(arrays), 1)
+    for name, a in arrays.items():
+        if isinstance(a, torch.Tensor):
+            a = a.detach().to("cpu", torch.float64 if a.dtype == torch.float64 else torch.float32).numpy()
+        a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+        if a.nbytes > share:
+            keep = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[keep]
+        np.save(out / (name + (f"_rank{rank}" if rank else "") + ".npy"), a)
+
+
+SETTLE_SECONDS = 0.25
+
+
+def settle(step, seconds=SETTLE_SECONDS):
+    """Untimed steps until the GPU's clocks have settled, before the warm-up
+    of a plain run.  From idle the first ~100 ms of steps run 5-8 % slow
+    (0.41 ms per step falling to 0.375 after ~250 steps, again after 2 s of
+    idling), and 10 warm-up steps are 4 ms: without this a plain run measured
+    242-243k audio-s/s where the full run, whose calibration passes precede
+    its timed region, measured 253.5k on the same box.  The step counter is
+    reset afterwards, so the timed steps see the same clip pairs on every run."""
+    t0 = time.perf_counter()
+    while time.perf_counter() - t0 < seconds:
+        for _ in range(25):
+            step()
+        torch.cuda.synchronize()
+    step.k, step.issued = 0, -1
 
 
 def collect(owner_stages, n_win):
@@ -531,6 +603,40 @@ def emit_line(out):
     print(compact_line(out, rel), flush=True)
 
 
+def max_over_ranks(elapsed, world, rank, cdev, step):
+    """The slowest rank's wall time of the timed region; with N ranks also the
+    per-file result gather (§8e): every rank's per-track records to all."""
+    t = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
+    if world > 1:
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        from aa_amd import shard
+        rec = torch.from_numpy(shard.pack_records([2 * rank, 2 * rank + 1], [0, 0], step.tmean.cpu().numpy(),
+                                                  width=step.model.n_labels)).to(cdev)
+        gathered = shard.gather_records(rec)
+        assert gathered.shape[0] == 2 * world
+    return float(t.item())
+
+
+def step_line(args, world, ppg, step, elapsed, workload):
+    """The contract's fields of a --config 2 run from its timed region."""
+    audio_s = world * args.steps * step.n_win * SECONDS_PER_WINDOW
+    return {
+        "metric": METRIC, "value": round(audio_s / elapsed, 1), "unit": "audio-s/s", "n_gpus": max(1, world // ppg),
+        "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(1e3 * elapsed / args.steps, 4), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None,
+        "dtype": args.precision + (" (fp16 log-mel)" if args.logmel == "f16" else ""),
+        "data": f"synthetic (48 kHz int16-quantised noise+chirps, seeded), seeded random-init {args.model}",
+        "config": {"workload": workload, "model": args.model, "global_batch": step.n_win * world,
+                   "seq_len": step.fe_s.win_len, "parallelism": f"dp{world}",
+                   "pipeline": f"{len(step.lanes)} batches in flight on {len(step.lanes)} streams"
+                               if step.lanes is not None else
+                               "front end of batch k+1 on a second stream beside the CNN of batch k"
+                               if step.pipeline else "serial",
+                   "clip_pairs": f"{HEAD_PAIRS} resident clip pairs in rotation, one per step"},
+    }
+
+
 def main_step(args, world, rank, dev, emit=True):
     from tools.make_models import make_model
     tmp = tempfile.mkdtemp(prefix="aa_bench_")
@@ -554,6 +660,21 @@ def main_step(args, world, rank, dev, emit=True):
     step = Step(dev, rank, model_path, args.precision, pairs=HEAD_PAIRS, first=first, lm16=args.logmel == "f16",
                 pipeline=args.pipeline, fe_s=fe_s)
     fe, model, n_win = step.fe, step.model, step.n_win
+    # collectives on the device over RCCL; on the host when ranks share a GPU (gloo)
+    cdev = dev if (world > 1 and dist.get_backend() == "nccl") else torch.device("cpu")
+    ppg = max(1, args.procs_per_gpu) if args.config in (2, 4) else 1  # as worker() places ranks
+
+    if not args.full:
+        # the plain run: settle the clocks, warm up, time the steps, print the line
+        settle(step)
+        elapsed = timed(step, args.steps, args.warmup, world)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, step.outputs(), rank)
+        elapsed = max_over_ranks(elapsed, world, rank, cdev, step)
+        out = step_line(args, world, ppg, step, elapsed, workload)
+        if emit and rank == 0:
+            print(compact_line(out), flush=True)
+        return out
 
     for _ in range(args.warmup):
         step()
@@ -611,19 +732,9 @@ def main_step(args, world, rank, dev, emit=True):
     if not (pipelined or lanes is not None):
         dom_serial = dom_live
     dom["owner"].set_timing(False)
-    # collectives on the device over RCCL; on the host when ranks share a GPU (gloo)
-    cdev = dev if (world > 1 and dist.get_backend() == "nccl") else torch.device("cpu")
-    ppg = max(1, args.procs_per_gpu) if args.config in (2, 4) else 1  # as worker() places ranks
-    t = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
-    if world > 1:
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        # the per-file result gather (§8e): every rank's per-track records to all
-        from aa_amd import shard
-        rec = torch.from_numpy(shard.pack_records([2 * rank, 2 * rank + 1], [0, 0], step.tmean.cpu().numpy(),
-                                                  width=model.n_labels)).to(cdev)
-        gathered = shard.gather_records(rec)
-        assert gathered.shape[0] == 2 * world
-    elapsed = float(t.item())
+    if args.dump_outputs and emit:  # (the headline's, not a secondary's)
+        dump_outputs(args.dump_outputs, step.outputs(), rank)
+    elapsed = max_over_ranks(elapsed, world, rank, cdev, step)
 
     is_fe = dom["owner"] is fe
     if is_fe and dom["name"].startswith("fe_stft"):
@@ -708,23 +819,8 @@ def main_step(args, world, rank, dev, emit=True):
                               "frac_of_matrix_peak": round(roofline["step_tflops"] / PEAK[args.precision], 4),
                               "frac_of_ceiling": round(ceil_s / (elapsed / args.steps), 4)}
 
-    audio_s = world * args.steps * n_win * SECONDS_PER_WINDOW
-    out = {
-        "metric": METRIC, "value": round(audio_s / elapsed, 1), "unit": "audio-s/s", "n_gpus": max(1, world // ppg),
-        "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(1e3 * elapsed / args.steps, 4), "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None,
-        "dtype": args.precision + (" (fp16 log-mel)" if args.logmel == "f16" else ""),
-        "data": f"synthetic (48 kHz int16-quantised noise+chirps, seeded), seeded random-init {args.model}",
-        "config": {"workload": workload, "model": args.model, "global_batch": n_win * world,
-                   "seq_len": step.fe_s.win_len, "parallelism": f"dp{world}",
-                   "pipeline": f"{len(step.lanes)} batches in flight on {len(step.lanes)} streams"
-                               if step.lanes is not None else
-                               "front end of batch k+1 on a second stream beside the CNN of batch k"
-                               if step.pipeline else "serial",
-                   "clip_pairs": f"{HEAD_PAIRS} resident clip pairs in rotation, one per step"},
-        "roofline": roofline,
-    }
+    out = step_line(args, world, ppg, step, elapsed, workload)
+    out["roofline"] = roofline
     gate_fail = None
     cfg = fe_config(step.fe_s)
     ref = None
@@ -903,6 +999,8 @@ def run_stream(args, world, rank, dev, clips=None, roofline=False):
         dist.barrier()
     elapsed = time.perf_counter() - t0
     assert len(results) == n_clips
+    if args.dump_outputs and clips is None:  # (--config 3 itself, not the secondary of a --full run)
+        dump_outputs(args.dump_outputs, {"track_scores": np.stack([s for _, _, s in results])}, rank)
     t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     n_gathered = len(results)
     if world > 1:

@@ -50,6 +50,36 @@ def test_secondaries_are_scalars(record):
     assert sec["f32"]["gate"] is True and "gate" not in sec["bf16"]
 
 
+def test_plain_run_is_the_default():
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 3)
+    assert bench.parse(["--full"]).full is True
+    assert bench.parse(["--dump-outputs", "d"]).dump_outputs == "d"
+    with pytest.raises(SystemExit):
+        bench.parse(["--config", "4", "--dump-outputs", "d"])
+
+
+def test_dump_outputs_float_arrays_within_the_limit(tmp_path, monkeypatch):
+    """float16 -> float32, float64 kept, an array beyond its share of the
+    limit written as the same sorted sample of its elements on every run."""
+    import numpy as np
+    import torch
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 3 * 400)
+    big = np.arange(1000, dtype=np.float32).reshape(10, 100) * 0.5
+    arrays = {"h": torch.arange(6, dtype=torch.float16).reshape(2, 3), "d": np.linspace(0, 1, 5), "big": big}
+    bench.dump_outputs(tmp_path / "a", arrays)
+    bench.dump_outputs(tmp_path / "b", arrays, rank=1)
+    got = {p.stem: np.load(p) for p in (tmp_path / "a").glob("*.npy")}
+    assert set(got) == {"h", "d", "big"}
+    assert got["h"].dtype == np.float32 and got["h"].tolist() == [[0, 1, 2], [3, 4, 5]]
+    assert got["d"].dtype == np.float64 and np.array_equal(got["d"], arrays["d"])
+    assert got["big"].dtype == np.float32 and got["big"].shape == (100,)
+    assert sum(a.nbytes for a in got.values()) <= 3 * 400
+    idx = (got["big"] * 2).astype(int)  # the elements kept: distinct, in order
+    assert np.all(np.diff(idx) > 0) and np.array_equal(big.reshape(-1)[idx], got["big"])
+    assert np.array_equal(np.load(tmp_path / "b" / "big_rank1.npy"), got["big"])
+
+
 def test_oversized_line_raises(record):
     big = dict(record)
     big["data"] = "x" * 9000

@@ -3,6 +3,7 @@
 # usage (through gpurun): [AB_ARGS="--model effnetv2"] bash tools/ab.sh ROUNDS lib1 lib2 ...   (paths; "main" = the in-tree libaa.so)
 set -o pipefail
 R=$1; shift
+AB_ARGS="--full ${AB_ARGS:-}"  # the stage tables read below are part of the full run only
 mkdir -p gpurun_out
 for r in $(seq 1 $R); do
   for L in "$@"; do

@@ -20,6 +20,7 @@
 set -o pipefail
 export TMPDIR=/tmp
 mkdir -p gpurun_out
+LOGS=$(mktemp -d)  # stdout / stderr of the full bench runs (their records go to bench_full.json)
 MODE=${1:-round}
 [ $# -gt 0 ] && shift
 PT="python -u -m pytest -x -q --timeout 300 --timeout-method thread"
@@ -51,9 +52,9 @@ round)
       cp gpurun_out/pmc_traffic_$P.json "$PROFILE_DIR/" && cp gpurun_out/stats_serial_$P/run_kernel_stats.csv "$PROFILE_DIR/bench_kernel_stats_serial_$P.csv" || exit 9
     done
   fi
-  timeout -k 10 500 python bench.py > gpurun_out/bench.log 2> gpurun_out/bench.err || { cat gpurun_out/bench.err; exit 7; }
+  timeout -k 10 600 python bench.py --full > $LOGS/bench.log 2> $LOGS/bench.err || { cat $LOGS/bench.err; exit 7; }
   cat gpurun_out/kernel_stats_serial_bf16x3.txt
-  tail -1 gpurun_out/bench.log
+  tail -1 $LOGS/bench.log
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke.log 2>&1 || { tail -20 gpurun_out/smoke.log; exit 8; }
   tail -2 gpurun_out/smoke.log
   ;;
@@ -79,7 +80,8 @@ sn)
 graph)
   timeout -k 10 400 $PT tests/test_gpu_graph.py > gpurun_out/graph_tests.log 2>&1 || { tail -30 gpurun_out/graph_tests.log; exit 1; }
   tail -1 gpurun_out/graph_tests.log
-  timeout -k 10 300 python bench.py --model effnetv2 --steps 20 --warmup 5 --cpu-seconds 0 --secondary=serial > gpurun_out/graph_bench.json 2> gpurun_out/graph_bench.err || { tail -20 gpurun_out/graph_bench.err; exit 2; }
+  timeout -k 10 300 python bench.py --full --model effnetv2 --steps 20 --warmup 5 --cpu-seconds 0 --secondary=serial > $LOGS/graph_bench.json 2> $LOGS/graph_bench.err || { tail -20 $LOGS/graph_bench.err; exit 2; }
+  tail -1 $LOGS/graph_bench.json
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/graphprof -o run -- python3 bench.py --model effnetv2 --steps 20 --warmup 5 --cpu-seconds 0 --secondary= --pipeline 0 --no-parity > gpurun_out/graphp.log 2>&1 || exit 3
   python tools/prof_summary.py gpurun_out/graphprof > gpurun_out/graph_kernel_stats_serial.txt && head -30 gpurun_out/graph_kernel_stats_serial.txt
   ;;

@@ -5,13 +5,14 @@
 set -o pipefail
 R=$1; shift
 mkdir -p gpurun_out
+LOG=$(mktemp)  # a run's stdout + stderr (the last line is the bench line)
 for r in $(seq 1 $R); do
   for V in "$@"; do
     [ "$V" = "-" ] && V=""
-    env $V timeout -k 10 200 python bench.py --model effnetv2 --steps 20 --warmup 5 --cpu-seconds 0 --secondary= --no-parity > gpurun_out/gab.log 2>&1 || { tail -5 gpurun_out/gab.log; exit 1; }
-    python - "${V:--}" <<'PY'
+    env $V timeout -k 10 200 python bench.py --full --model effnetv2 --steps 20 --warmup 5 --cpu-seconds 0 --secondary= --no-parity > "$LOG" 2>&1 || { tail -5 "$LOG"; exit 1; }
+    python - "${V:--}" "$LOG" <<'PY'
 import json, sys
-d = json.loads(open("gpurun_out/gab.log").read().strip().splitlines()[-1])
+d = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])
 d = json.load(open("gpurun_out/bench_full.json")) if "stages_ms" not in d["roofline"] else d  # (the printed line is compact)
 import re
 g = {}
