@@ -222,6 +222,38 @@ class Model(_lib.StageTiming):
     def predict(self, x: torch.Tensor) -> torch.Tensor:
         return self.forward(x)[1]
 
+    def stage_shape(self, k: int):
+        """(Hout, Wout, C_out) of stage k's stored activations; raises AAError
+        for a stage that never reaches memory (fused away, or the logits)."""
+        if self.graph:
+            raise _lib.AAError("stage_shape: graph models have no stage read-out")
+        h, w, c = C.c_int32(), C.c_int32(), C.c_int32()
+        _lib.check(_lib.lib().aa_model_stage_shape(self._h, int(k), C.byref(h), C.byref(w), C.byref(c)),
+                   "aa_model_stage_shape")
+        return h.value, w.value, c.value
+
+    def forward_prefix(self, x: torch.Tensor, k: int, stream=None) -> torch.Tensor:
+        """Stages 0..k as ``forward`` launches them, then stage k's stored
+        output decoded exactly to float32 [n, Hout, Wout, C_out]."""
+        h, w, c = self.stage_shape(k)
+        n = int(x.shape[0])
+        if tuple(x.shape[1:]) != self.in_shape:
+            raise ValueError(f"input {tuple(x.shape)} != model input {self.in_shape}")
+        if x.dtype not in (torch.float32, torch.float16):
+            raise ValueError(f"input dtype {x.dtype}: float32 or float16")
+        f16 = x.dtype == torch.float16
+        if f16 != self._in_f16:  # as forward does: the first stage reads the dtype it is told
+            _lib.check(_lib.lib().aa_model_set_input_f16(self._h, int(f16)), "aa_model_set_input_f16")
+            self._in_f16 = f16
+        act = torch.empty((n, h, w, c), dtype=torch.float32, device=self.device)
+        if n == 0:
+            return act
+        ws = self._workspace(n)
+        _lib.check(_lib.lib().aa_model_forward_prefix(self._h, _lib.dptr(x), n, int(k), _lib.dptr(act), _lib.dptr(ws),
+                                                      int(ws.numel()), _lib.stream_ptr(stream)),
+                   "aa_model_forward_prefix")
+        return act
+
 
 def track_mean(probs: torch.Tensor, win_begin: torch.Tensor, win_count: torch.Tensor,
                out: torch.Tensor = None, stream=None) -> torch.Tensor:

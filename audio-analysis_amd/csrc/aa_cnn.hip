@@ -1090,6 +1090,38 @@ __global__ void track_mean(const float* __restrict__ probs, int n_models, long l
 namespace aa {
 
 // ---------------------------------------------------------------------------
+// Stage read-out (aa_model_forward_prefix): whatever a stage stored, as plain
+// f32 NHWC.  MODE 0: f32 copied; 1: bf16 -> f32; 2: e4m3fn -> f32 (exact, bit
+// arithmetic); 3: the grouped-split layout (aa_conv_x3.h: per pixel and
+// 32-channel group 64 B of bf16 hi, then 64 B of bf16 lo) -> hi + lo, which
+// is exact in f32 (lo is a multiple of the split value's f32 ulp).
+// ---------------------------------------------------------------------------
+template <int MODE>
+__global__ void stage_decode(const void* __restrict__ src, float* __restrict__ dst, size_t total, int cout) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        float v;
+        if (MODE == 0) {
+            v = static_cast<const float*>(src)[i];
+        } else if (MODE == 1) {
+            v = __uint_as_float((uint32_t) static_cast<const uint16_t*>(src)[i] << 16);
+        } else if (MODE == 2) {
+            const uint32_t b = static_cast<const uint8_t*>(src)[i];
+            const int e = (b >> 3) & 15, m = b & 7;
+            const float a = (e == 15 && m == 7) ? __uint_as_float(0x7fc00000u)
+                            : e == 0            ? ldexpf((float)m, -9)
+                                                : ldexpf((float)(8 + m), e - 10);
+            v = (b & 0x80) ? -a : a;
+        } else {
+            const size_t pix = i / (size_t)cout;
+            const int c = (int)(i - pix * (size_t)cout);
+            const uint16_t* h = static_cast<const uint16_t*>(src) + pix * (size_t)cout * 2 + (size_t)(c >> 5) * 64 + (c & 31);
+            v = __uint_as_float((uint32_t)h[0] << 16) + __uint_as_float((uint32_t)h[32] << 16);
+        }
+        dst[i] = v;
+    }
+}
+
+// ---------------------------------------------------------------------------
 // host: planner, workspace, forward, timing
 // ---------------------------------------------------------------------------
 // ST_SMALL: C_in = 1 3x3 -> 32 first conv (VALU, fusable into the next
@@ -2085,6 +2117,70 @@ extern "C" int aa_model_stage_time(void* model, int32_t stage, double* total_ms,
     Model* m = static_cast<Model*>(model);
     AA_CHECK(m && stage >= 0 && stage < (int)m->st.size(), AA_ERR_INVALID, "aa_model_stage_time: bad stage");
     return m->timer.collect(stage, total_ms, count);
+}
+
+extern "C" int aa_model_stage_shape(const void* model, int32_t stage, int32_t* h, int32_t* w, int32_t* c) {
+    const Model* m = static_cast<const Model*>(model);
+    AA_CHECK(m && stage >= 0 && stage < (int)m->st.size(), AA_ERR_INVALID, "aa_model_stage_shape: bad stage");
+    const Stage& s = m->st[stage];
+    // stages whose output never reaches memory as activations: a first conv
+    // computed inside the next stage, the conv inside the fused tail, the logits
+    AA_CHECK(!s.skipped, AA_ERR_UNSUPPORTED, "aa_model_stage_shape: stage %d (%s) is computed inside stage %d and never stored",
+             stage, s.name.c_str(), stage + 1);
+    AA_CHECK(s.kind != ST_POOLDENSE && s.kind != ST_HEAD, AA_ERR_UNSUPPORTED,
+             "aa_model_stage_shape: stage %d (%s) writes the logits, not activations", stage, s.name.c_str());
+    if (h) *h = s.Hout;
+    if (w) *w = s.Wout;
+    if (c) *c = s.cout;
+    return AA_OK;
+}
+
+extern "C" int aa_model_forward_prefix(void* model, const void* x, int32_t n, int32_t stage, float* act,
+                                       void* workspace, size_t workspace_bytes, void* stream) {
+    Model* m = static_cast<Model*>(model);
+    AA_CHECK(m && x && act, AA_ERR_INVALID, "aa_model_forward_prefix: null argument");
+    int32_t sh, sw, sc;
+    const int src = aa_model_stage_shape(model, stage, &sh, &sw, &sc);
+    if (src != AA_OK) return src;
+    AA_CHECK(n >= 0 && n <= 32768, AA_ERR_INVALID, "aa_model_forward_prefix: n %d outside 0..32768", n);
+    if (n == 0) return AA_OK;
+    const size_t need = aa_model_workspace_bytes(m, n);
+    AA_CHECK(workspace && workspace_bytes >= need, AA_ERR_WORKSPACE, "aa_model_forward_prefix: workspace %zu < %zu",
+             workspace_bytes, need);
+    // the buffers and the launches of aa_model_forward, stages 0..stage
+    const size_t es = prec_bytes(m->prec);
+    char* buf[2] = {static_cast<char*>(workspace),
+                    static_cast<char*>(workspace) + align_up(m->act_elems[0] * es * n, 256)};
+    float* tmp = reinterpret_cast<float*>(buf[1] + align_up(m->act_elems[1] * es * n, 256));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const void* in = x;
+    for (int32_t k = 0; k <= stage; ++k) {
+        const Stage& s = m->st[k];
+        if (s.skipped) continue;
+        void* out = buf[k % 2];
+        const Stage* first = s.fused_first ? &m->st[k - 1] : nullptr;
+        const int rc = m->prec == AA_PREC_BF16     ? launch_stage<bf16>(*m, s, in, out, nullptr, nullptr, n, st, first, tmp)
+                       : m->prec == AA_PREC_FP8    ? launch_stage<fp8>(*m, s, in, out, nullptr, nullptr, n, st, first, tmp)
+                       : m->prec == AA_PREC_BF16X3 ? launch_stage<bf16x3>(*m, s, in, out, nullptr, nullptr, n, st, first, tmp)
+                                                   : launch_stage<float>(*m, s, in, out, nullptr, nullptr, n, st, first, tmp);
+        if (rc != AA_OK) return rc;
+        in = out;
+    }
+    const Stage& s = m->st[stage];
+    const size_t total = (size_t)n * sh * sw * sc;
+    const unsigned blocks = (unsigned)std::min<size_t>((total + 255) / 256, 65536);
+    // ST_SMALL / ST_GENERIC / ST_GCONV store the mode's plain activation type;
+    // only a conv_x3 / conv_wg stage with out_split writes the grouped split
+    if (s.out_split)
+        hipLaunchKernelGGL(stage_decode<3>, dim3(blocks), dim3(256), 0, st, in, act, total, sc);
+    else if (m->prec == AA_PREC_BF16)
+        hipLaunchKernelGGL(stage_decode<1>, dim3(blocks), dim3(256), 0, st, in, act, total, sc);
+    else if (m->prec == AA_PREC_FP8)
+        hipLaunchKernelGGL(stage_decode<2>, dim3(blocks), dim3(256), 0, st, in, act, total, sc);
+    else
+        hipLaunchKernelGGL(stage_decode<0>, dim3(blocks), dim3(256), 0, st, in, act, total, sc);
+    AA_LAUNCH_CHECK();
+    return AA_OK;
 }
 
 extern "C" int aa_track_mean(const float* probs, int32_t n_models, int64_t model_stride, int32_t n_labels,

@@ -824,8 +824,12 @@ void conv_x3(const float* __restrict__ in, int Hin, int Win, const bf16* __restr
         if (!(DIAG & 2) && !AJIT) read_a(F0, 0);
         // a wave whose fragments all lie in tile rows past the conv output
         // (the bottom tile row of a tall tile) skips its MFMAs: those outputs
-        // are discarded by the epilogue
-        const bool wave_idle = oh0 + (wm * MF * 16) / TW >= Hout * POOL;
+        // are discarded by the epilogue.  Not with the weight ring: there a
+        // step also holds the wave's share of the next slice's loads and the
+        // barrier that publishes it, so a wave that skipped its steps left
+        // the others reading slices that never arrived (garbage in every
+        // output of a bottom tile with few valid rows)
+        const bool wave_idle = !RING && oh0 + (wm * MF * 16) / TW >= Hout * POOL;
         if constexpr (DIAG & 4096) ts[1] = __builtin_amdgcn_s_memtime();
         // AA_X3_PRIO (A/B knob): the wave's MFMA steps at a raised issue
         // priority, so waves of co-resident blocks still staging (VALU) fill

@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define AA_ABI_VERSION 2
+#define AA_ABI_VERSION 3
 
 typedef enum aa_status {
     AA_OK = 0,
@@ -179,6 +179,21 @@ int aa_model_stage_info(const void* model, int32_t stage, char* name, int32_t na
                         double* flops_per_item, double* bytes_per_item);
 int aa_model_set_timing(void* model, uint32_t stage_mask);
 int aa_model_stage_time(void* model, int32_t stage, double* total_ms, int64_t* count);
+
+/* Read-out of one stage's activations, for per-stage checks against a
+ * reference.  stage_shape: Hout, Wout, C_out of what the stage stores (any
+ * pointer may be NULL); AA_ERR_UNSUPPORTED, with the reason in
+ * aa_last_error, for a stage whose output never reaches memory as
+ * activations: a first conv computed inside the next stage, the conv inside
+ * the fused tail, and the stage that writes the logits.
+ * forward_prefix: launches stages 0..stage exactly as aa_model_forward does
+ * (same kernels, flags and workspace layout), then decodes that stage's
+ * stored output to act, device float32 [n][Hout][Wout][C_out]: f32 copied,
+ * bf16 / e4m3fn widened, the split-bf16 grouped layout summed hi + lo -- all
+ * exact.  Allocates nothing; n <= 32768; workspace as for aa_model_forward. */
+int aa_model_stage_shape(const void* model, int32_t stage, int32_t* h, int32_t* w, int32_t* c);
+int aa_model_forward_prefix(void* model, const void* x, int32_t n, int32_t stage, float* act,
+                            void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------- CNN graphs (DAG models: residual / squeeze-excite / depthwise) ---------------- */
 /* Models that are not a single conv chain -- Keras Functional graphs such as

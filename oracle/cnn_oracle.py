@@ -378,3 +378,316 @@ def ensemble_track_mean(probs_per_model):
     """np.mean over models then over windows (src/identify_tracks.py:548-551)."""
     p = np.mean(probs_per_model, axis=0)
     return np.mean(p, axis=0)
+
+
+# ---------------------------------------------------------------------------
+# One stage at a time: float64 reference + derived bound + interval rule
+# (DESIGN.md "Per-stage checks").  A stage is what one kernel launch of
+# aa_model_forward computes: one conv block (conv [BN] [act] [pool]), or the
+# fused first pair (two blocks), read from the stage's ACTUAL input (the GPU's
+# decoded output of the previous stored stage), so errors do not accumulate
+# and a failure names one kernel.
+# ---------------------------------------------------------------------------
+U24 = 2.0 ** -24        # f32 unit roundoff
+SPLIT_C = 2.0 ** -15    # split-bf16 direct kernels: 3 * 2^-18 per product (dropped lo.lo, bf16 rounding of lo), margin 2
+
+
+def conv_blocks(arch):
+    """The arch as conv blocks, one per libaa stage, in stage order:
+    ([[conv, bn?, act?, pool?] layer dicts, ...], the layers after the last
+    block).  Block k is stage k of aa_model_create's plan."""
+    blocks, i = [], 0
+    while i < len(arch) and arch[i]["type"] != "conv2d":
+        if arch[i]["type"] == "magtransform":
+            raise NotImplementedError("stage reference: MagTransform models")
+        i += 1
+    while i < len(arch) and arch[i]["type"] == "conv2d":
+        blk = [arch[i]]
+        i += 1
+        for kind in ("batchnorm", ("leakyrelu", "relu"), "maxpool2d"):
+            if i < len(arch) and arch[i]["type"] in (kind if isinstance(kind, tuple) else (kind,)):
+                blk.append(arch[i])
+                i += 1
+        blocks.append(blk)
+    return blocks, arch[i:]
+
+
+def _fold_block(tensors, blk):
+    """(w64 [O, I, kh, kw] with the BN scale folded in, shift64 [O], slope or
+    None, pool or None) of one conv block, as aa_model_create folds it."""
+    t = lambda k: torch.from_numpy(np.asarray(tensors[k])).double()
+    conv = blk[0]
+    w = t(conv["name"] + ".kernel").permute(3, 2, 0, 1)
+    shift = t(conv["name"] + ".bias") if conv.get("use_bias", False) else torch.zeros(w.shape[0], dtype=torch.float64)
+    slope, pool = None, None
+    for ly in blk[1:]:
+        if ly["type"] == "batchnorm":
+            nm = ly["name"]
+            sc = t(nm + ".gamma") / torch.sqrt(t(nm + ".moving_variance") + float(np.float32(ly.get("eps", 1e-3))))
+            shift = (shift - t(nm + ".moving_mean")) * sc + t(nm + ".beta")
+            w = w * sc[:, None, None, None]
+        elif ly["type"] == "leakyrelu":
+            slope = float(np.float32(ly.get("alpha", 0.3)))
+        elif ly["type"] == "relu":
+            slope = 0.0
+        elif ly["type"] == "maxpool2d":
+            pool = tuple(ly["pool"])
+    return w, shift, slope, pool
+
+
+def _bf16r(x):
+    return x.float().to(torch.bfloat16).double()
+
+
+def _split16(x):
+    """hi + lo of an f32 value as the kernels form it (bf16 hi, bf16 lo of the
+    exact remainder): what an OUT_SPLIT store keeps and a fused first layer reads."""
+    x = x.float()
+    hi = x.to(torch.bfloat16).float()
+    return (hi + (x - hi).to(torch.bfloat16).float()).double()
+
+
+def _fp8_quant(w32):
+    """aa_model_create's e4m3fn weights: per output channel s = 240 / amax in
+    f32, q = e4m3fn(w * s); (q, 1 / s) as f32 tensors."""
+    amax = w32.abs().amax(dim=(1, 2, 3))
+    s = torch.where(amax > 0, 240.0 / amax, torch.ones_like(amax))
+    return _fp8(w32 * s[:, None, None, None]), 1.0 / s
+
+
+def _act32(v, slope):
+    if slope is None:
+        return v
+    return torch.where(v >= 0, v, v * np.float32(slope))
+
+
+def stage_store(v64, slope, pool, storage, ebf16=False):
+    """The kernels' epilogue after the accumulator, applied as they apply it
+    (f32 arithmetic): [bf16 epilogue tile] -> max pool -> activation ->
+    rounding to the storage type ("f32", "split": the grouped-split hi + lo,
+    "bf16", "fp8").  Every step is monotone non-decreasing, so the chain maps
+    an interval of pre-activation values to the interval of stored values.
+    v64: [N, C, H, W] float64; returns float64."""
+    v = v64.float()
+    if ebf16:
+        v = v.to(torch.bfloat16).float()
+    if pool is not None and tuple(pool) != (1, 1):
+        v = F.max_pool2d(v, pool, pool)
+    v = _act32(v, slope)
+    if storage == "split":
+        return _split16(v)
+    if storage == "bf16":
+        v = v.to(torch.bfloat16).float()
+    elif storage == "fp8":
+        v = _fp8(v)
+    else:
+        assert storage == "f32", storage
+    return v.double()
+
+
+def _absconv(x, w, shift):
+    return F.conv2d(x.abs(), w.abs()) + shift.abs()[None, :, None, None]
+
+
+def _trunc_slack(xmag, wq, inv_s):
+    """fp8 MFMA truncation: every product of a group of 8 loses < 2^(E - 13),
+    2^E <= the group's largest max(|a|, 2^-6) * max(|b|, 2^-6), so a group
+    loses < 2^-10 of the sum of those.  Upper bound of that loss per output."""
+    lo = 2.0 ** -6
+    return 2.0 ** -10 * F.conv2d(xmag.clamp(min=lo), wq.double().abs().clamp(min=lo)) * inv_s.double()[None, :, None, None]
+
+
+def _stage_pre(tensors, stage_layers, x_in, precision, kernel="direct", c_wg=None):
+    """(centre y, bound B) of the last block's accumulator + shift, float64
+    [N, C, Hc, Wc], plus that block's (slope, pool)."""
+    blocks, rest = conv_blocks(list(stage_layers))
+    assert blocks and not rest and len(blocks) in (1, 2), "a stage is one conv block or the fused first pair"
+    x = torch.from_numpy(np.ascontiguousarray(x_in)).double().permute(0, 3, 1, 2)
+    col = lambda v: v[None, :, None, None]
+    w, shift, slope, pool = _fold_block(tensors, blocks[-1])
+    K = w.shape[1] * w.shape[2] * w.shape[3]
+    if len(blocks) == 2:
+        # fused first pair: a C_in = 1 3x3 conv and its activation, then the block above
+        w1, s1, slope1, pool1 = _fold_block(tensors, blocks[0])
+        assert w1.shape[1] == 1 and pool1 is None and (slope1 is None or 0.0 <= slope1 <= 1.0)
+        K1 = w1.shape[2] * w1.shape[3]
+        act = lambda v: v if slope1 is None else torch.where(v >= 0, v, v * slope1)
+        if precision in ("f32", "bf16x3"):
+            sp = SPLIT_C if precision == "bf16x3" else 0.0
+            y1 = F.conv2d(x, w1) + col(s1)
+            B1 = ((K1 + 8) * U24 + sp) * _absconv(x, w1, s1)
+            h1 = act(y1)  # |act(a) - act(b)| <= |a - b| for a slope in [0, 1]
+            y = F.conv2d(h1, w) + col(shift)
+            A = _absconv(h1.abs() + B1, w, shift)
+            B = F.conv2d(B1, w.abs()) + ((K + 8) * U24 + sp) * A
+            return y, B, slope, pool
+        # bf16 / fp8: bf16 weights on the input as bf16 hi + lo, f32 sums from
+        # the bias, the activation, then bf16 / e4m3fn into the patch
+        q = (lambda v: v.to(torch.bfloat16).float()) if precision == "bf16" else _fp8
+        w1q, b1 = _bf16r(w1.float()), s1.float().double()
+        x16 = _split16(x)
+        y1 = F.conv2d(x16, w1q) + col(b1)
+        B1 = (K1 + 8) * U24 * _absconv(x16, w1q, b1)
+        h = [q(_act32(v.float(), slope1)).double() for v in (y1 - B1, y1, y1 + B1)]
+        hmag = torch.maximum(h[0].abs(), h[2].abs())
+        dh = h[2] - h[0]
+        b2 = shift.float().double()
+        if precision == "bf16":
+            wq = _bf16r(w.float())
+            y = F.conv2d(h[1], wq) + col(b2)
+            B = F.conv2d(dh, wq.abs()) + (K + 8) * U24 * _absconv(hmag, wq, b2)
+        else:
+            wq, inv_s = _fp8_quant(w.float())
+            acc = _fp8_mfma_conv(h[1].float(), wq, k128=False, lchunk=64)
+            y = acc.double() * col(inv_s.double()) + col(b2)
+            weff = wq.double() * inv_s.double()[:, None, None, None]
+            # beyond the issue's |W2| (*) interval term: the centre is the TRUNCATING emulation on h[1],
+            # and an intermediate one e4m3fn step away changes which product bits its groups truncate;
+            # both runs lose < _trunc_slack, hence 2 x, and only where some intermediate is two-valued
+            touched = (F.conv2d((dh != 0).double(), (wq != 0).double()) > 0).double()
+            B = (F.conv2d(dh, weff.abs()) + 2.0 * _trunc_slack(hmag, wq, inv_s) * touched +
+                 (K + 8) * U24 * _absconv(hmag, weff, b2))
+        return y, B, slope, pool
+    if w.shape[1] == 1 or precision == "f32" or precision == "bf16x3":
+        # f32 arithmetic (conv_small in every mode), the f32 MFMA chain, or split-bf16
+        y = F.conv2d(x, w) + col(shift)
+        A = _absconv(x, w, shift)
+        c = (K + 8) * U24
+        if precision == "bf16x3" and w.shape[1] > 1:
+            if kernel == "wg":
+                assert c_wg is not None, "the Winograd constant comes from the emulation (winograd_constant)"
+                c += c_wg
+            else:
+                c += SPLIT_C
+        return y, c * A, slope, pool
+    b = shift.float().double()
+    if precision == "bf16":
+        wq = _bf16r(w.float())
+        y = F.conv2d(x, wq) + col(b)
+        return y, (K + 8) * U24 * _absconv(x, wq, b), slope, pool
+    assert precision == "fp8", precision
+    wq, inv_s = _fp8_quant(w.float())
+    acc = _fp8_mfma_conv(x.float(), wq, k128=w.shape[1] >= 64, lchunk=64)
+    y = acc.double() * col(inv_s.double()) + col(b)
+    weff = wq.double() * inv_s.double()[:, None, None, None]
+    return y, (K + 8) * U24 * _absconv(x, weff, b), slope, pool
+
+
+def _storage(precision, out_split):
+    return "split" if out_split else {"f32": "f32", "bf16x3": "f32", "bf16": "bf16", "fp8": "fp8"}[precision]
+
+
+def _pooled(y, B, slope, pool):
+    if pool is not None and tuple(pool) != (1, 1):
+        y, B = F.max_pool2d(y, pool, pool), F.max_pool2d(B, pool, pool)
+    if slope is not None:
+        y = torch.where(y >= 0, y, y * slope)
+        B = B * max(1.0, slope)
+    return y.permute(0, 2, 3, 1).numpy(), B.permute(0, 2, 3, 1).numpy()
+
+
+@torch.no_grad()
+def stage_reference(arch, tensors, stage_layers, x_in, precision, kernel="direct", c_wg=None):
+    """(r, B), float64 NHWC at the stage's output shape.  r: the stage's
+    layers in float64 on x_in (bf16 / fp8: with the weights as
+    aa_model_create stores them; fp8: summed as the MFMAs sum, the project's
+    emulation).  B: how far correct arithmetic of that precision may sit from
+    r, per element: the pre-activation bound (see _stage_pre / DESIGN.md)
+    taken through the max pool (the largest of the window) and the
+    activation (slope <= 1 keeps it).  ``arch`` is not needed (the stage's
+    layers carry their names); kept for call sites that pass it."""
+    return _pooled(*_stage_pre(tensors, stage_layers, x_in, precision, kernel, c_wg))
+
+
+@torch.no_grad()
+def stage_check(tensors, stage_layers, x_in, precision, kernel="direct", c_wg=None, ebf16=False, out_split=False):
+    """One evaluation of the stage for the interval rule: dict of float64 NHWC
+    arrays r, B (stage_reference), lo = store(y - B), hi = store(y + B) and
+    mid = store(y), `store` being the stage's own epilogue chain
+    (stage_store).  A stored element g is correct iff lo <= g <= hi."""
+    y, B, slope, pool = _stage_pre(tensors, stage_layers, x_in, precision, kernel, c_wg)
+    # (conv_small, a stand-alone C_in = 1 first conv, has no epilogue tile)
+    small = np.asarray(x_in).shape[-1] == 1 and len(conv_blocks(list(stage_layers))[0]) == 1
+    st = _storage(precision, out_split)
+    e = bool(ebf16) and precision in ("bf16", "fp8") and not small
+    out = {k: stage_store(v, slope, pool, st, e).permute(0, 2, 3, 1).numpy()
+           for k, v in (("lo", y - B), ("hi", y + B), ("mid", y))}
+    out["r"], out["B"] = _pooled(y, B, slope, pool)
+    return out
+
+
+def stage_interval(arch, tensors, stage_layers, x_in, precision, kernel="direct", c_wg=None, ebf16=False,
+                   out_split=False):
+    """(lo, hi) of stage_check."""
+    d = stage_check(tensors, stage_layers, x_in, precision, kernel, c_wg, ebf16, out_split)
+    return d["lo"], d["hi"]
+
+
+@torch.no_grad()
+def head_interval(tensors, stage_layers, x_in, precision):
+    """(lo, hi, r) of the logits [N, L] of a 1x1 head + global max, float64:
+    stage_layers = [the head conv] (conv_head + head_final on the stored
+    activations x_in), or [conv block, head conv] for split-bf16's fused tail
+    (aa_conv_tail.h: the conv, bias, activation, hi / lo split and the head in
+    one launch).  The bound goes through the 1x1 head like any conv and
+    through the maximum over pixels, which is monotone."""
+    blocks, rest = conv_blocks(list(stage_layers))
+    assert not rest and len(blocks) in (1, 2)
+    x = torch.from_numpy(np.ascontiguousarray(x_in)).double().permute(0, 3, 1, 2)
+    col = lambda v: v[None, :, None, None]
+    w, shift, slope, pool = _fold_block(tensors, blocks[-1])
+    assert tuple(w.shape[2:]) == (1, 1) and pool is None
+    K = w.shape[1]
+    if len(blocks) == 2:
+        assert precision == "bf16x3"
+        y6, B6, s6, p6 = _stage_pre(tensors, blocks[0], x_in, "bf16x3")
+        assert p6 is None
+        h6 = y6 if s6 is None else torch.where(y6 >= 0, y6, y6 * s6)
+        B6 = B6 * max(1.0, s6 or 0.0)
+        y = F.conv2d(h6, w) + col(shift)
+        B = F.conv2d(B6, w.abs()) + (SPLIT_C + (K + 8) * U24) * _absconv(h6.abs() + B6, w, shift)
+    elif precision in ("f32", "bf16x3"):  # the exact-f32 MFMA on f32 activations
+        y = F.conv2d(x, w) + col(shift)
+        B = (K + 8) * U24 * _absconv(x, w, shift)
+    elif precision == "bf16":
+        wq, b = _bf16r(w.float()), shift.float().double()
+        y = F.conv2d(x, wq) + col(b)
+        B = (K + 8) * U24 * _absconv(x, wq, b)
+    else:
+        wq, inv_s = _fp8_quant(w.float())
+        b = shift.float().double()
+        y = _fp8_mfma_conv(x.float(), wq, k128=K >= 64).double() * col(inv_s.double()) + col(b)
+        B = (K + 8) * U24 * _absconv(x, wq.double() * inv_s.double()[:, None, None, None], b)
+    fin = lambda v: _act32(torch.amax(v, dim=(2, 3)).float(), slope).double().numpy()
+    return fin(y - B), fin(y + B), fin(y)
+
+
+def winograd_constant(tensors, stage_layers, x_in, wo, tables):
+    """c_wg of a Winograd F(wo, 3) stage on these inputs: 4 x the largest
+    |emulation - r| / A, the emulation being tools/wino_study.conv_wino (f32
+    transforms, split-bf16 products) with the kernel's tables (A^T, G, B^T)."""
+    from tools.wino_study import conv_wino
+    blocks, _ = conv_blocks(list(stage_layers))
+    w, shift, _, _ = _fold_block(tensors, blocks[-1])
+    x = torch.from_numpy(np.ascontiguousarray(x_in)).double().permute(0, 3, 1, 2)
+    r = F.conv2d(x, w) + shift[None, :, None, None]
+    A = _absconv(x, w, shift)
+    e = conv_wino(x, w, shift, wo, None, tables=tables)
+    return 4.0 * float(((e - r).abs() / A).max())
+
+
+def interval_violations(g, lo, hi):
+    """Elements of g outside [lo, hi] (NaN and Inf outside any interval):
+    (count, index of the worst one or None, its excess over the interval's
+    half width, in half widths -- inf for a non-finite g)."""
+    g, lo, hi = np.asarray(g, np.float64), np.asarray(lo), np.asarray(hi)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        ok = np.isfinite(g) & (g >= lo) & (g <= hi)
+        out = np.maximum(lo - g, g - hi) / np.maximum((hi - lo) / 2, np.finfo(np.float64).tiny)
+    out = np.where(np.isfinite(g), out, np.inf)
+    out = np.where(ok, 0.0, out)
+    n = int((~ok).sum())
+    if not n:
+        return 0, None, 0.0
+    idx = np.unravel_index(int(np.argmax(out)), g.shape)
+    return n, tuple(int(i) for i in idx), float(out[idx])

@@ -1,45 +1,18 @@
-"""Diagnostic: the fused first-layer pair (conv_wgf vs conv_x3, AA_WGF=1/0)
-through aa_model on calibrated networks against the oracle: model1 and a
-two-conv chain (3x3 1->32, 3x3 32->32 + pool 3, GlobalMaxPool2D), whose
-"logits" are the pooled maxima of the pair's own output.
+"""Input for the conv_wgf harness (tools/wgf_check.hip, WGF_DATA): the BN-folded
+weights of a calibrated two-conv chain (3x3 1->32, 3x3 32->32 + pool 3) and the
+dB-like check input, as raw f32 files.  (conv_wgf lives in the tools/ harness
+only: libaa.so serves the pair with conv_x3, which
+tests/test_gpu_cnn_stages.py checks per element.)
 
-    python tools/wgf_model_check.py        (GPU box; runs each AA_WGF in a child)
+    python tools/wgf_model_check.py OUT_DIR
 """
-import os
-import subprocess
 import sys
-import tempfile
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
 for p in (str(ROOT), str(ROOT / "audio-analysis_amd")):
     if p not in sys.path:
         sys.path.insert(0, p)
-
-
-def child(tmp):
-    import numpy as np
-    import torch
-    from aa_amd.model import Model
-    from oracle import cnn_oracle
-    from tools.make_models import calibration_input, make_chain, make_model
-    tmp = Path(tmp)
-    for name in ("chain", "model1"):
-        p = tmp / name / "audioModel.safetensors"
-        if not p.exists():
-            if name == "chain":
-                make_chain(tmp / name, [(32, (3, 3), None), (32, (3, 3), (3, 3))])
-            else:
-                make_model(tmp / name, "model1", seed=1)
-        x = calibration_input(6, 160, 226, True, np.random.default_rng(232))
-        m = Model(p, x.shape[1:], precision="bf16x3")
-        lg, _ = m.forward(torch.from_numpy(x).cuda())
-        torch.cuda.synchronize()
-        lg = lg.cpu().numpy()
-        ref, _ = cnn_oracle.forward(p, x)
-        d = np.abs(lg - ref)
-        print(f"AA_WGF={os.environ.get('AA_WGF', '1')} {name}: max|d| {d.max():.3e} (ref {ref.min():.2f}..{ref.max():.2f}); "
-              f"worst logits by window {d.max(axis=1).round(4).tolist()}", flush=True)
 
 
 def dump(out):
@@ -71,12 +44,7 @@ def dump(out):
 
 
 if __name__ == "__main__":
-    if len(sys.argv) > 2 and sys.argv[1] == "--dump":
-        dump(sys.argv[2])
-    elif len(sys.argv) > 1:
-        child(sys.argv[1])
-    else:
-        tmp = tempfile.mkdtemp()
-        for v in ("0", "1"):
-            env = dict(os.environ, AA_WGF=v)
-            subprocess.run([sys.executable, __file__, tmp], env=env, check=True)
+    args = [a for a in sys.argv[1:] if a != "--dump"]
+    if len(args) != 1:
+        sys.exit(__doc__)
+    dump(args[0])

@@ -74,11 +74,14 @@ def conv_split(x, w, b):
     return (y + b[None, :, None, None]).float().double()
 
 
-def conv_wino(x, w, b, m, pts, presplit=False):
+def conv_wino(x, w, b, m, pts, presplit=False, tables=None):
     """The kh x 3 valid conv through F(m, 3) along W: input transform in f32,
     weight transform in f64, both split, products exact, output transform in
-    f32 (outputs past the last whole group computed on zero columns and cut)."""
-    AT, G, BT = toom_cook(m, 3, pts)
+    f32 (outputs past the last whole group computed on zero columns and cut).
+    tables: (A^T, G, B^T) to use instead of toom_cook(m, 3, pts), e.g. the
+    ones a kernel compiles in."""
+    AT, G, BT = tables if tables is not None else toom_cook(m, 3, pts)
+    AT, G, BT = (np.asarray(t, np.float64) for t in (AT, G, BT))
     a = m + 2
     N, C, H, W = x.shape
     O, _, kh, kw = w.shape
