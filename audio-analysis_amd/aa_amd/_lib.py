@@ -16,7 +16,7 @@ import torch  # noqa: F401  (must precede loading libaa.so, see above)
 
 # AA_LIB: an alternative build of the same library (tools/ab_build.py variants)
 LIB_PATH = Path(os.environ.get("AA_LIB") or Path(__file__).resolve().parent / "libaa.so")
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 AA_PREC_F32 = 0
 AA_PREC_BF16 = 1
@@ -142,6 +142,10 @@ _SIGS = {
                                        C.POINTER(C.c_int32)]),
     "aa_model_forward_prefix": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                           C.c_size_t, C.c_void_p]),
+    "aa_model_plan": (C.c_int, [C.POINTER(Layer), C.c_int32, C.c_void_p, C.c_int64, C.c_int32,
+                                C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "aa_model_stage_image": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t,
+                                       C.POINTER(C.c_size_t)]),
     "aa_graph_create": (C.c_int, [C.POINTER(Node), C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
                                   C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
     "aa_graph_destroy": (C.c_int, [C.c_void_p]),

@@ -3,24 +3,28 @@
 // Replaces model.predict(np.array(d)) (reference src/identify_tracks.py:544,
 // Keras on TF-CPU) for the layer family the build defines:
 //   [MagTransform] conv-BN-act [maxpool] ... conv1x1 globalmax sigmoid
-// Planner (aa_model_create) folds each BatchNormalization into the preceding
-// conv, fuses the activation and a following 3x3/3 max-pool into the conv's
-// epilogue, and the final 1x1 conv + GlobalMaxPool2D + sigmoid into one head
-// kernel.  Stages:
-//   conv_small  first layer (C_in = 1): VALU, f32 math, MagTransform prologue
-//               (src/magtransformv2.py:19-21), writes NHWC activations.
-//   conv_mfma   C_in % 32 == 0: implicit GEMM, M = output pixels of a
-//               TH x TW tile, N = output channels, K = kh*kw*C_in.  The input
-//               patch (TH+kh-1) x (TW+kw-1) x C_in is staged once in LDS
-//               (16-B vector loads, +16 B channel pad per pixel); A fragments
-//               come from LDS, B fragments (weights, [C_out][K], L2-resident)
-//               from global.  bf16: v_mfma_f32_16x16x32_bf16; f32 parity mode:
-//               v_mfma_f32_16x16x4_f32 (exact f32 fma chain), same fragment
-//               layout with K permuted inside each 32-chunk.  Epilogue stages
-//               the f32 tile in LDS, applies max-pool, bias (folded BN) and the
-//               activation, and stores NHWC.
-//   conv_head   1x1 conv + global max over all pixels + sigmoid, one block per
-//               window, A fragments straight from global.
+// Four precisions (aa.h): f32 parity, bf16, fp8 (e4m3fn, per-channel weight
+// scales) and split-bf16 (f32 activations, bf16 hi + lo operands: the default).
+//
+// This file holds, in order:
+//   * the precision tags, MFMA fragment helpers and the kernels every
+//     precision shares: conv_small (C_in = 1 first conv, VALU), conv_mfma
+//     (tuned implicit-GEMM conv for f32 / bf16 / fp8: patch staged once in
+//     LDS, weight slices streamed through an LDS ring by global_load_lds,
+//     K = 128 super-steps for fp8 at C_in >= 64, optional fused first conv,
+//     max-pool + bias + activation epilogue), conv_head + head_final (1x1
+//     conv, global max, sigmoid), conv_generic / pool_dense (f32 VALU
+//     fallbacks for any other shape), track_mean, stage_decode;
+//   * the split-bf16 kernel families, each in its own header: aa_conv_x3.h
+//     (direct), aa_conv_wg.h (Winograd along W), aa_gconv.h (runtime-shaped),
+//     aa_conv_tail.h (last conv + head in one launch);
+//   * aa_cnn_plan.h: Stage, Model and the host-only planner (layer list ->
+//     stages with packed weight images), over aa_cnn_tiles.h (tile tables)
+//     and aa_cnn_pack.h (weight layouts);
+//   * the launchers (one shared prologue for the tuned convs, launch_stage
+//     choosing the instantiation from the tile tables), upload_model,
+//     run_stages (the one stage loop behind aa_model_forward and
+//     aa_model_forward_prefix) and the aa_model_* entry points.
 #include "aa_common.h"
 
 #include <cmath>
@@ -1121,55 +1125,41 @@ __global__ void stage_decode(const void* __restrict__ src, float* __restrict__ d
     }
 }
 
+}  // namespace aa
+
+#include "aa_cnn_plan.h"
+
+namespace aa {
+
 // ---------------------------------------------------------------------------
-// host: planner, workspace, forward, timing
+// host: launchers, upload, forward, timing
 // ---------------------------------------------------------------------------
-// ST_SMALL: C_in = 1 3x3 -> 32 first conv (VALU, fusable into the next
-// stage); ST_MFMA: tuned matrix-core conv; ST_HEAD: 1x1 conv + global max;
-// ST_GENERIC: any other conv shape / pool window (f32 VALU fallback);
-// ST_POOLDENSE: GlobalMaxPool2D [+ Dense] [+ sigmoid] after a conv stage;
-// ST_GCONV: split-bf16 mode, a conv with C_in >= 16 and no tuned tile: the
-// runtime-shaped MFMA kernel gconv_x3 (aa_gconv.h) [+ gpool2d for the max pool]
-enum StageKind { ST_SMALL = 0, ST_MFMA = 1, ST_HEAD = 2, ST_GENERIC = 3, ST_POOLDENSE = 4, ST_GCONV = 5 };
-
-struct Stage {
-    int kind = ST_MFMA;
-    int kh = 1, kw = 1, cin = 0, cout = 0, cout_pad = 0;
-    int pool = 1;        // square pool window of the tuned kernels (1 or 3), 0 otherwise
-    int ph = 1, pw = 1;  // max-pool window (= strides)
-    int act = ACT_NONE;
-    float alpha = 0.f;
-    int has_mag = 0;
-    float mag_exp = 1.f;
-    int sigmoid = 0;
-    int Hin = 0, Win = 0, Hc = 0, Wc = 0, Hout = 0, Wout = 0;
-    void* d_w = nullptr;
-    float* d_b = nullptr;
-    double flops = 0, bytes = 0;  // algorithmic per window
-    std::string name;
-    int skipped = 0;    // first layer computed inside the next stage
-    int is_first = 0;   // reads the model input (f32 log-mel)
-    int fused_first = 0;  // this stage computes the previous (first) layer itself
-    int lm_f16 = 0;       // fused_first: the model input is float16
-    int in_split = 0;     // split-bf16: input / output in the grouped-split layout (aa_conv_x3.h)
-    int out_split = 0;
-    int wg = 0;           // split-bf16 Winograd F(wg, 3)-along-W kernel (aa_conv_wg.h, wg = WO) and its weight packing
-    int wg_npass = 1;     // its staging passes (planes per pass = (wg + 2) / wg_npass)
-    int cin_pad = 0;      // ST_GCONV: C_in rounded up to 32
-    int tail = 0;         // ST_HEAD, split-bf16: computes the previous conv stage itself (aa_conv_tail.h)
-    void* d_tw = nullptr;  // tail: head weights packed per wave / label fragment, hi then lo
-};
-
-struct Model {
-    int prec = AA_PREC_BF16;
-    int in_h = 0, in_w = 0, in_c = 0;
-    int L = 0;
-    std::vector<Stage> st;
-    size_t act_elems[2] = {0, 0};  // per-window elements of the ping-pong buffers
-    size_t tmp_elems = 0;          // per-window f32 elements of an ST_GCONV stage's unpooled output
-    StageTimer timer;  // HIP events around the stages in timer.mask
-};
-
+// What the tuned conv launchers (conv_mfma, conv_x3, conv_wg) share: the fused
+// first conv's arguments (`first` non-null), the kernel's LDS limit, and the
+// grid of POOL-aligned TH x TW tiles x BN-channel blocks x windows.  window32:
+// the kernel addresses one window's activations through buffer resources
+// based at the window (64-bit) with 32-bit offsets inside it.  Then
+// launch(grid, tiles_w, fc) starts the kernel.
+template <typename Launch>
+static int launch_tuned(const Stage& s, const Stage* first, int n, const void* kernel, size_t lds, bool window32,
+                        int pool, int th, int tw, int bn, Launch&& launch) {
+    if (window32)
+        AA_CHECK((double)s.Hin * s.Win * s.cin * 4 < 2147483647.0, AA_ERR_UNSUPPORTED,
+                 "conv %s: one window's activations exceed 2 GiB", s.name.c_str());
+    FirstConv fc{};
+    if (first) {
+        const float slope = first->act == ACT_LEAKY ? first->alpha : first->act == ACT_RELU ? 0.f : 1.f;
+        fc = FirstConv{(const float*)first->d_w, first->d_b, first->act, slope, first->has_mag,
+                       first->mag_exp, first->Hin, first->Win, s.lm_f16};
+    }
+    AA_CHECK(lds <= 160 * 1024, AA_ERR_UNSUPPORTED, "conv %s: %zu B LDS", s.name.c_str(), lds);
+    AA_DYN_LDS(kernel, lds);
+    const int tiles_h = (s.Hout * pool + th - 1) / th;
+    const int tiles_w = (s.Wout * pool + tw - 1) / tw;
+    launch(dim3(tiles_h * tiles_w, s.cout_pad / bn, n), tiles_w, fc);
+    AA_LAUNCH_CHECK();
+    return AA_OK;
+}
 
 template <typename T, int KH, int KW, int CIN, int WM, int WN, int MF, int NF, int POOL, int TH, int TW,
           bool FUSED = false, bool EBF16 = false, int OCC = 0>
@@ -1178,119 +1168,13 @@ static int launch_mfma(const Stage& s, const void* in, void* out, int n, hipStre
     auto k = conv_mfma<T, KH, KW, CIN, WM, WN, MF, NF, POOL, TH, TW, FUSED, 0, EBF16, OCC>;
     constexpr int BN = WN * NF * 16;
     const size_t lds = conv_lds_bytes<T, KH, KW, CIN, BN, TH, TW, FUSED, EBF16>();
-    FirstConv fc{};
-    if (FUSED) {
-        const float slope = first->act == ACT_LEAKY ? first->alpha : first->act == ACT_RELU ? 0.f : 1.f;
-        fc = FirstConv{(const float*)first->d_w, first->d_b, first->act, slope, first->has_mag,
-                       first->mag_exp, first->Hin, first->Win, s.lm_f16};
-    }
-    AA_CHECK(lds <= 160 * 1024, AA_ERR_UNSUPPORTED, "conv %s: %zu B LDS", s.name.c_str(), lds);
-    AA_DYN_LDS(k, lds);
-    const int tiles_h = (s.Hout * POOL + TH - 1) / TH;
-    const int tiles_w = (s.Wout * POOL + TW - 1) / TW;
-    dim3 grid(tiles_h * tiles_w, s.cout_pad / BN, n);
     using GT = typename Prec<T>::G;
     using LT = typename Prec<T>::L;
-    hipLaunchKernelGGL(k, grid, dim3(WM * WN * 64), lds, st, (const GT*)in, s.Hin, s.Win, (const LT*)s.d_w, s.d_b,
-                       (GT*)out, s.Hout, s.Wout, s.cout, tiles_w, s.act, s.alpha, fc);
-    AA_LAUNCH_CHECK();
-    return AA_OK;
-}
-
-// Tile configuration of every conv_mfma instantiation, one line per
-// (dtype, kernel, C_in, pool): waves (WM x WN), 16x16 fragments per wave
-// (MF x NF), output tile TH x TW, bf16 epilogue tile.  BN = WN * NF * 16
-// output channels per block.  The f32 rows are the parity mode (smaller
-// tiles: the same LDS budget holds half the elements).
-#define AA_CONV_CFGS(X)                                     \
-    X(bf16, 3, 3, 32, 3, 4, 1, 6, 2, 18, 21, true, 0)          \
-    X(bf16, 3, 3, 32, 1, 2, 2, 4, 2, 8, 16, true, 0)           \
-    X(bf16, 3, 3, 64, 1, 2, 2, 4, 2, 8, 16, true, 0)           \
-    X(bf16, 9, 3, 64, 3, 4, 2, 6, 4, 39, 9, true, 0)           \
-    X(bf16, 1, 3, 128, 1, 2, 4, 5, 2, 7, 20, false, 0)         \
-    X(fp8, 3, 3, 32, 3, 4, 1, 6, 2, 12, 30, true, 0)           \
-    X(fp8, 3, 3, 32, 1, 2, 2, 4, 2, 8, 16, true, 0)            \
-    X(fp8, 3, 3, 64, 1, 4, 1, 3, 4, 12, 16, true, 0)           \
-    X(fp8, 9, 3, 64, 3, 4, 2, 6, 4, 21, 18, true, 0)           \
-    X(fp8, 1, 3, 128, 1, 2, 4, 5, 2, 7, 20, true, 0)           \
-    X(float, 3, 3, 32, 3, 2, 2, 9, 1, 6, 48, false, 0)         \
-    X(float, 3, 3, 32, 1, 1, 4, 9, 1, 6, 24, false, 0)         \
-    X(float, 3, 3, 64, 1, 1, 4, 9, 1, 6, 24, false, 0)         \
-    X(float, 9, 3, 64, 3, 1, 4, 7, 1, 3, 33, false, 0)         \
-    X(float, 1, 3, 128, 1, 2, 2, 5, 1, 6, 24, false, 0)
-
-// conv_x3 (split-bf16) instantiations: (kernel, C_in, pool) -> waves (WM x
-// WN), fragments per wave (MF x NF), output tile TH x TW, weight ring in LDS
-// (1) or per-wave B fragments from global (0), A fragments just in time (1)
-// or a whole step ahead (0), pinned waves per SIMD (0: free); picked by
-// tools/conv_bench_x3.hip sweeps
-#ifdef AA_X3_ALT  // tools/ab_build.py: an alternative tile table for in-pipeline A/B runs
-#define AA_X3_CFGS(X) AA_X3_ALT(X)
-#else
-#define AA_X3_CFGS(X)                                 \
-    X(3, 3, 32, 3, 4, 1, 4, 2, 12, 21, 0, 1, 0)       \
-    X(3, 3, 32, 1, 4, 2, 3, 2, 10, 18, 1, 0, 4)       \
-    X(3, 3, 64, 1, 2, 2, 3, 2, 12, 8, 1, 1, 0)        \
-    X(9, 3, 64, 3, 2, 2, 4, 2, 21, 6, 0, 1, 4)        \
-    X(1, 3, 128, 1, 2, 2, 3, 2, 7, 12, 1, 1, 0)
-#endif
-
-// conv_wg (split-bf16, Winograd F(WO,3) along W) instantiations: (kh, C_in,
-// pool) of kernel-width-3 convs -> waves (WM x WN), fragments per wave (MF x
-// NF, each with WO + 2 accumulator sets), output tile TH x TW (TW a multiple
-// of WO), pinned waves per SIMD (0: free), outputs per group WO, staging
-// passes NPASS, B fragment sets in flight BD.  Preferred over conv_x3 where a row exists (the
-// fused first-layer stage always runs conv_x3).  In-pipeline A/B (tools/ab.sh,
-// same box): the 9x3 layer 187 -> 160 us, step 180k -> 193k audio-s/s; the
-// small 3x3 / 1x3 layers lose on it (their transform-heavy staging outweighs
-// the saved MFMAs: 3x3/32 36 -> 55 us, 3x3/64 52 -> 76 us, 1x3 22 -> 28 us).
-#ifdef AA_WG_ALT
-#define AA_WG_CFGS(X) AA_WG_ALT(X)
-#else
-// F(6,3) for the 9x3 layer (in-pipeline A/B, 3 rounds on one box: 9x3 131 ->
-// 122 us, step 260k -> 264k; F(4,3) on 39x12 tiles 140 us, F(3,3) spills):
-// 8 planes of the 39 x 6 tile's single column group, 4 waves of 16 output
-// channels each, 96 accumulator VGPRs
-#define AA_WG_CFGS(X) X(9, 64, 3, 1, 4, 3, 1, 39, 6, 0, 6, 1, 2)
-#endif
-
-static int wg_bn(int kh, int kw, int cin, int pool) {
-#define AA_WBN(KH, CIN, POOL, WM, WN, MF, NF, TH, TW, OCC, WO, NPASS, BD) \
-    if (kw == 3 && kh == KH && cin == CIN && pool == POOL) return WN * NF * 16;
-    AA_WG_CFGS(AA_WBN)
-#undef AA_WBN
-    return 0;
-}
-// (WO, NPASS) of the Winograd instantiation serving a stage
-static void wg_form(int kh, int cin, int pool, int* wo, int* npass) {
-#define AA_WFORM(KH, CIN, POOL, WM, WN, MF, NF, TH, TW, OCC, WO, NPASS, BD) \
-    if (kh == KH && cin == CIN && pool == POOL) { *wo = WO; *npass = NPASS; return; }
-    AA_WG_CFGS(AA_WFORM)
-#undef AA_WFORM
-    *wo = 0;
-    *npass = 1;
-}
-
-template <typename T>
-constexpr int prec_of() {
-    return is_split<T>() ? AA_PREC_BF16X3 : sizeof(T) == 1 ? AA_PREC_FP8 : sizeof(T) == 2 ? AA_PREC_BF16 : AA_PREC_F32;
-}
-// bytes of one stored activation (split-bf16 keeps f32 activations)
-static size_t prec_bytes(int prec) { return prec == AA_PREC_FP8 ? 1 : prec == AA_PREC_BF16 ? 2 : 4; }
-
-// output channels per block of the instantiation serving this stage (0: none)
-static int mfma_bn(int prec, int kh, int kw, int cin, int pool) {
-    if (prec == AA_PREC_BF16X3 && wg_bn(kh, kw, cin, pool)) return wg_bn(kh, kw, cin, pool);
-#define AA_BN(T_, KH, KW, CIN, POOL, WM, WN, MF, NF, TH, TW, EB, OCC)                                       \
-    if (prec_of<T_>() == prec && kh == KH && kw == KW && cin == CIN && pool == POOL) \
-        return WN * NF * 16;
-    AA_CONV_CFGS(AA_BN)
-#undef AA_BN
-#define AA_BN3(KH, KW, CIN, POOL, WM, WN, MF, NF, TH, TW, RING, AJIT, OCC)                                               \
-    if (prec == AA_PREC_BF16X3 && kh == KH && kw == KW && cin == CIN && pool == POOL) return WN * NF * 16;
-    AA_X3_CFGS(AA_BN3)
-#undef AA_BN3
-    return 0;
+    return launch_tuned(s, FUSED ? first : nullptr, n, (const void*)k, lds, false, POOL, TH, TW, BN,
+                        [&](dim3 grid, int tiles_w, const FirstConv& fc) {
+        hipLaunchKernelGGL(k, grid, dim3(WM * WN * 64), lds, st, (const GT*)in, s.Hin, s.Win, (const LT*)s.d_w, s.d_b,
+                           (GT*)out, s.Hout, s.Wout, s.cout, tiles_w, s.act, s.alpha, fc);
+    });
 }
 
 template <int KH, int KW, int CIN, int WM, int WN, int MF, int NF, int POOL, int TH, int TW, bool RING, bool AJIT,
@@ -1298,26 +1182,12 @@ template <int KH, int KW, int CIN, int WM, int WN, int MF, int NF, int POOL, int
 static int launch_x3(const Stage& s, const void* in, void* out, int n, hipStream_t st, const Stage* first) {
     auto k = conv_x3<KH, KW, CIN, WM, WN, MF, NF, POOL, TH, TW, FUSED, 0, RING, AJIT, OCC, IN_SPLIT, OUT_SPLIT>;
     constexpr int BN = WN * NF * 16;
-    // buffer-resource addressing: the resources are based at the window
-    // (64-bit), offsets inside one window are 32-bit
-    AA_CHECK((double)s.Hin * s.Win * s.cin * 4 < 2147483647.0, AA_ERR_UNSUPPORTED,
-             "conv %s: one window's activations exceed 2 GiB", s.name.c_str());
     const size_t lds = x3_lds_bytes<KH, KW, CIN, BN, TH, TW, FUSED, RING>();
-    FirstConv fc{};
-    if (FUSED) {
-        const float slope = first->act == ACT_LEAKY ? first->alpha : first->act == ACT_RELU ? 0.f : 1.f;
-        fc = FirstConv{(const float*)first->d_w, first->d_b, first->act, slope, first->has_mag,
-                       first->mag_exp, first->Hin, first->Win, s.lm_f16};
-    }
-    AA_CHECK(lds <= 160 * 1024, AA_ERR_UNSUPPORTED, "conv %s: %zu B LDS", s.name.c_str(), lds);
-    AA_DYN_LDS(k, lds);
-    const int tiles_h = (s.Hout * POOL + TH - 1) / TH;
-    const int tiles_w = (s.Wout * POOL + TW - 1) / TW;
-    dim3 grid(tiles_h * tiles_w, s.cout_pad / BN, n);
-    hipLaunchKernelGGL(k, grid, dim3(WM * WN * 64), lds, st, (const float*)in, s.Hin, s.Win, (const bf16*)s.d_w,
-                       s.d_b, (float*)out, s.Hout, s.Wout, s.cout, tiles_w, s.act, s.alpha, fc);
-    AA_LAUNCH_CHECK();
-    return AA_OK;
+    return launch_tuned(s, FUSED ? first : nullptr, n, (const void*)k, lds, true, POOL, TH, TW, BN,
+                        [&](dim3 grid, int tiles_w, const FirstConv& fc) {
+        hipLaunchKernelGGL(k, grid, dim3(WM * WN * 64), lds, st, (const float*)in, s.Hin, s.Win, (const bf16*)s.d_w,
+                           s.d_b, (float*)out, s.Hout, s.Wout, s.cout, tiles_w, s.act, s.alpha, fc);
+    });
 }
 
 template <int KH, int CIN, int WM, int WN, int MF, int NF, int POOL, int TH, int TW, int OCC, int WO, int NPASS,
@@ -1325,18 +1195,27 @@ template <int KH, int CIN, int WM, int WN, int MF, int NF, int POOL, int TH, int
 static int launch_wg(const Stage& s, const void* in, void* out, int n, hipStream_t st) {
     auto k = conv_wg<KH, CIN, WM, WN, MF, NF, POOL, TH, TW, OCC, IN_SPLIT, OUT_SPLIT, 0, WO, NPASS, BD>;
     constexpr int BN = WN * NF * 16;
-    AA_CHECK((double)s.Hin * s.Win * s.cin * 4 < 2147483647.0, AA_ERR_UNSUPPORTED,
-             "conv %s: one window's activations exceed 2 GiB", s.name.c_str());
     const size_t lds = wg_lds_bytes<KH, BN, TH, TW, WO, NPASS, WN>();
-    AA_CHECK(lds <= 160 * 1024, AA_ERR_UNSUPPORTED, "conv %s: %zu B LDS", s.name.c_str(), lds);
-    AA_DYN_LDS(k, lds);
-    const int tiles_h = (s.Hout * POOL + TH - 1) / TH;
-    const int tiles_w = (s.Wout * POOL + TW - 1) / TW;
-    dim3 grid(tiles_h * tiles_w, s.cout_pad / BN, n);
-    hipLaunchKernelGGL(k, grid, dim3(WM * WN * 64), lds, st, (const float*)in, s.Hin, s.Win, (const bf16*)s.d_w,
-                       s.d_b, (float*)out, s.Hout, s.Wout, s.cout, tiles_w, s.act, s.alpha);
-    AA_LAUNCH_CHECK();
-    return AA_OK;
+    return launch_tuned(s, nullptr, n, (const void*)k, lds, true, POOL, TH, TW, BN,
+                        [&](dim3 grid, int tiles_w, const FirstConv&) {
+        hipLaunchKernelGGL(k, grid, dim3(WM * WN * 64), lds, st, (const float*)in, s.Hin, s.Win, (const bf16*)s.d_w,
+                           s.d_b, (float*)out, s.Hout, s.Wout, s.cout, tiles_w, s.act, s.alpha);
+    });
+}
+
+// A split-bf16 stage's runtime (fused_first, in_split, out_split) as template
+// arguments: f(fused, in_split, out_split) with std::true_type / false_type.
+// A fused first conv reads the f32 log-mel, never the split layout, and only
+// a kernel shape that CAN_FUSE is instantiated with it.
+template <bool CAN_FUSE, typename F>
+static int dispatch_split(const Stage& s, F&& f) {
+    using Y = std::true_type;
+    using N = std::false_type;
+    if constexpr (CAN_FUSE) {
+        if (s.fused_first) return s.out_split ? f(Y{}, N{}, Y{}) : f(Y{}, N{}, N{});
+    }
+    if (s.in_split) return s.out_split ? f(N{}, Y{}, Y{}) : f(N{}, Y{}, N{});
+    return s.out_split ? f(N{}, N{}, Y{}) : f(N{}, N{}, N{});
 }
 
 template <typename T>
@@ -1404,14 +1283,9 @@ static int launch_stage(const Model& m, const Stage& s, const void* in, void* ou
             // the last conv stage and the head in one launch (aa_conv_tail.h):
             // per-tile label maxima into `out`, then head_final over the tiles
             const Stage& c = *first;
-#ifndef AA_TAIL_TW  // (A/B knobs: tile width and pixel fragments per wave)
-#define AA_TAIL_TW 5
-#define AA_TAIL_MF 5
-#endif
-            constexpr int TH = 13, TW = AA_TAIL_TW;
-            const int tiles_h = (c.Hc + TH - 1) / TH, tiles_w = (c.Wc + TW - 1) / TW;
-            auto k = conv_tail_x3<1, 3, 128, AA_TAIL_MF, TH, TW>;
-            constexpr size_t lds = tail_lds_bytes<1, 3, 128, TH, TW>();
+            const int tiles_h = (c.Hc + TAIL_TH - 1) / TAIL_TH, tiles_w = (c.Wc + TAIL_TW - 1) / TAIL_TW;
+            auto k = conv_tail_x3<1, 3, 128, AA_TAIL_MF, TAIL_TH, TAIL_TW>;
+            constexpr size_t lds = tail_lds_bytes<1, 3, 128, TAIL_TH, TAIL_TW>();
             AA_DYN_LDS(k, lds);
             float* part = static_cast<float*>(out);
             hipLaunchKernelGGL(k, dim3(tiles_h * tiles_w, 1, n), dim3(TAIL_NW * 64), lds, st, (const float*)in, c.Hin,
@@ -1452,37 +1326,26 @@ static int launch_stage(const Model& m, const Stage& s, const void* in, void* ou
     }
     if constexpr (is_split<T>()) {
         if (s.wg) {
-#define AA_LAUNCHW(KH, CIN, POOL, WM, WN, MF, NF, TH, TW, OCC, WO, NPASS, BD)                                       \
-            if (s.kh == KH && s.cin == CIN && s.pool == POOL) {                                                   \
-                if (s.in_split)                                                                                   \
-                    return s.out_split ? launch_wg<KH, CIN, WM, WN, MF, NF, POOL, TH, TW, OCC, WO, NPASS, BD, true, true>(s, in, out, n, st) \
-                                       : launch_wg<KH, CIN, WM, WN, MF, NF, POOL, TH, TW, OCC, WO, NPASS, BD, true, false>(s, in, out, n, st); \
-                return s.out_split ? launch_wg<KH, CIN, WM, WN, MF, NF, POOL, TH, TW, OCC, WO, NPASS, BD, false, true>(s, in, out, n, st) \
-                                   : launch_wg<KH, CIN, WM, WN, MF, NF, POOL, TH, TW, OCC, WO, NPASS, BD, false, false>(s, in, out, n, st); \
-            }
+#define AA_LAUNCHW(KH, CIN, POOL, WM, WN, MF, NF, TH, TW, OCC, WO, NPASS, BD)                                    \
+            if (s.kh == KH && s.cin == CIN && s.pool == POOL)                                                    \
+                return dispatch_split<false>(s, [&](auto, auto is, auto os) {                                    \
+                    return launch_wg<KH, CIN, WM, WN, MF, NF, POOL, TH, TW, OCC, WO, NPASS, BD, decltype(is)::value, \
+                                     decltype(os)::value>(s, in, out, n, st);                                    \
+                });
             AA_WG_CFGS(AA_LAUNCHW)
 #undef AA_LAUNCHW
             set_error("conv %dx%d cin %d pool %d: no Winograd kernel instantiation", s.kh, s.kw, s.cin, s.pool);
             return AA_ERR_UNSUPPORTED;
         }
-#define AA_X3L(FU, IS, OS) launch_x3<KH_, KW_, CIN_, WM_, WN_, MF_, NF_, POOL_, TH_, TW_, RING_, AJIT_, OCC_, FU, IS, OS>(s, in, out, n, st, first)
-#define AA_LAUNCH3(KH, KW, CIN, POOL, WM, WN, MF, NF, TH, TW, RING, AJIT, OCC)                            \
-        if (s.kh == KH && s.kw == KW && s.cin == CIN && s.pool == POOL) {                                  \
-            constexpr int KH_ = KH, KW_ = KW, CIN_ = CIN, WM_ = WM, WN_ = WN, MF_ = MF, NF_ = NF, POOL_ = POOL;  \
-            constexpr int TH_ = TH, TW_ = TW, OCC_ = OCC;                                                  \
-            constexpr bool RING_ = RING, AJIT_ = AJIT;                                                     \
-            if (s.fused_first) {                                                                           \
-                if constexpr (CIN == 32 && KH == 3 && KW == 3)                                             \
-                    return s.out_split ? AA_X3L(true, false, true) : AA_X3L(true, false, false);          \
-            } else if (s.in_split) {                                                                       \
-                return s.out_split ? AA_X3L(false, true, true) : AA_X3L(false, true, false);              \
-            } else {                                                                                       \
-                return s.out_split ? AA_X3L(false, false, true) : AA_X3L(false, false, false);            \
-            }                                                                                              \
-        }
+        // (only the 3x3/32 rows have a fused-first form: launch_stage checked the shape above)
+#define AA_LAUNCH3(KH, KW, CIN, POOL, WM, WN, MF, NF, TH, TW, RING, AJIT, OCC)                                   \
+        if (s.kh == KH && s.kw == KW && s.cin == CIN && s.pool == POOL)                                          \
+            return dispatch_split<CIN == 32 && KH == 3 && KW == 3>(s, [&](auto fu, auto is, auto os) {           \
+                return launch_x3<KH, KW, CIN, WM, WN, MF, NF, POOL, TH, TW, RING, AJIT, OCC, decltype(fu)::value, \
+                                 decltype(is)::value, decltype(os)::value>(s, in, out, n, st, first);            \
+            });
         AA_X3_CFGS(AA_LAUNCH3)
 #undef AA_LAUNCH3
-#undef AA_X3L
         set_error("conv %dx%d cin %d pool %d: no split-bf16 kernel instantiation", s.kh, s.kw, s.cin, s.pool);
         return AA_ERR_UNSUPPORTED;
     }
@@ -1504,512 +1367,120 @@ static int launch_stage(const Model& m, const Stage& s, const void* in, void* ou
     return AA_ERR_UNSUPPORTED;
 }
 
-// a C_in = 1 first conv (3x3 -> 32) the next 3x3/32 pooled MFMA stage computes itself
-static bool fusable_first(const Stage& a, const Stage& b) {
-    return a.kind == ST_SMALL && a.kh == 3 && a.kw == 3 && a.cin == 1 && a.cout == 32 && b.kind == ST_MFMA &&
-           b.cin == 32 && b.kh == 3 && b.kw == 3 && b.pool == 3 &&
-           (a.act != ACT_LEAKY || (a.alpha >= 0.f && a.alpha <= 1.f));
-}
-
 static void free_model(Model* m) {
     if (!m) return;
     m->timer.release();
-    for (auto& s : m->st) {
-        (void)hipFree(s.d_w);
-        (void)hipFree(s.d_b);
-        (void)hipFree(s.d_tw);
-    }
+    if (m->uploaded)
+        for (auto& s : m->st) {
+            (void)hipFree(s.d_w);
+            (void)hipFree(s.d_b);
+            (void)hipFree(s.d_tw);
+        }
     delete m;
 }
 
-static uint16_t f2bf(float f) {  // round to nearest even
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7fc0;
-    u += 0x7fff + ((u >> 16) & 1);
-    return (uint16_t)(u >> 16);
-}
-static float bf2f(uint16_t b) {
-    const uint32_t u = (uint32_t)b << 16;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
+// Copies every stage's host images to the device and releases them.
+static int upload_model(Model* m) {
+    m->uploaded = true;  // from here on the stages may own device memory
+    auto put = [](void** d, const void* h, size_t bytes) {
+        hipError_t e = hipMalloc(d, bytes ? bytes : 4);
+        if (e == hipSuccess && bytes) e = hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice);
+        return e;
+    };
+    for (Stage& s : m->st) {
+        hipError_t e = s.h_w.empty() ? hipSuccess : put(&s.d_w, s.h_w.data(), s.h_w.size());
+        if (e == hipSuccess) e = put((void**)&s.d_b, s.h_b.data(), sizeof(float) * s.h_b.size());
+        AA_CHECK(e == hipSuccess, AA_ERR_HIP, "aa_model_create: layer %d: %s", s.layer_end, hipGetErrorString(e));
+        if (!s.h_tw.empty()) e = put(&s.d_tw, s.h_tw.data(), s.h_tw.size());
+        AA_CHECK(e == hipSuccess, AA_ERR_HIP, "aa_model_create: %s", hipGetErrorString(e));
+        std::vector<uint8_t>().swap(s.h_w);
+        std::vector<uint8_t>().swap(s.h_tw);
+        std::vector<float>().swap(s.h_b);
+    }
+    return AA_OK;
 }
 
-// f32 -> OCP e4m3fn byte, round to nearest even, saturated to +-448 (the
-// device's v_cvt_pk_fp8_f32 conversion of the same value)
-static uint8_t f2fp8(float f) {
-    const uint8_t sgn = std::signbit(f) ? 0x80 : 0;
-    double a = std::fabs((double)f);
-    if (std::isnan(f)) return 0x7f;
-    if (a >= 448.0) return sgn | 0x7e;
-    if (a < std::ldexp(1.0, -6)) {  // subnormal: multiples of 2^-9
-        const int q = (int)std::nearbyint(a * 512.0);
-        return sgn | (uint8_t)q;  // q == 8 is the smallest normal's encoding
+// Stages 0 .. last_stage on n <= 32768 windows: the workspace carved into the
+// two ping-pong buffers and the ST_GCONV scratch, one launch_stage per stored
+// stage.  *last_out (optional): where stage last_stage wrote.
+template <typename T>
+static int run_stages_t(Model* m, const void* x, int n, int last_stage, float* logits, float* probs, void* workspace,
+                        hipStream_t st, bool timed, const void** last_out) {
+    const size_t es = prec_bytes(m->prec);
+    char* buf[2] = {static_cast<char*>(workspace),
+                    static_cast<char*>(workspace) + align_up(m->act_elems[0] * es * n, 256)};
+    float* tmp = reinterpret_cast<float*>(buf[1] + align_up(m->act_elems[1] * es * n, 256));
+    const void* in = x;
+    for (int k = 0; k <= last_stage; ++k) {
+        const Stage& s = m->st[k];
+        if (s.skipped) continue;  // computed inside stage k + 1 (reads x directly)
+        // (a fused tail writes its per-tile maxima into the skipped conv stage's
+        // buffer: its own would be the one its input lives in)
+        void* out = buf[(s.tail ? k - 1 : k) % 2];
+        const Stage* first = (s.fused_first || s.tail) ? &m->st[k - 1] : nullptr;
+        hipEvent_t e0 = nullptr;
+        int rc = timed ? m->timer.begin(k, st, &e0) : AA_OK;
+        if (rc != AA_OK) return rc;
+        rc = launch_stage<T>(*m, s, in, out, logits, probs, n, st, first, tmp);
+        if (rc != AA_OK) return rc;
+        rc = m->timer.end(k, st, e0);
+        if (rc != AA_OK) return rc;
+        in = out;
     }
-    int ex;
-    std::frexp(a, &ex);  // a = m 2^ex, m in [0.5, 1)
-    const int e = ex - 1;
-    double q = std::nearbyint(std::ldexp(a, 3 - e));  // 8 .. 16
-    int ee = e;
-    if (q >= 16.0) { q = 8.0; ++ee; }
-    if (ee > 8 || (ee == 8 && q > 14.0)) return sgn | 0x7e;
-    return sgn | (uint8_t)(((ee + 7) << 3) | ((int)q - 8));
+    if (last_out) *last_out = in;
+    return AA_OK;
+}
+
+static int run_stages(Model* m, const void* x, int n, int last_stage, float* logits, float* probs, void* workspace,
+                      hipStream_t st, bool timed, const void** last_out = nullptr) {
+    switch (m->prec) {
+        case AA_PREC_BF16: return run_stages_t<bf16>(m, x, n, last_stage, logits, probs, workspace, st, timed, last_out);
+        case AA_PREC_FP8: return run_stages_t<fp8>(m, x, n, last_stage, logits, probs, workspace, st, timed, last_out);
+        case AA_PREC_BF16X3: return run_stages_t<bf16x3>(m, x, n, last_stage, logits, probs, workspace, st, timed, last_out);
+        default: return run_stages_t<float>(m, x, n, last_stage, logits, probs, workspace, st, timed, last_out);
+    }
 }
 
 }  // namespace aa
 
 using namespace aa;
 
+extern "C" int aa_model_plan(const aa_layer* layers, int32_t n_layers, const float* blob, int64_t blob_len,
+                             int32_t in_h, int32_t in_w, int32_t in_c, int32_t precision, void** model) {
+    AA_CHECK(model, AA_ERR_INVALID, "aa_model_create: null argument");
+    Model* m = nullptr;
+    const int rc = plan_model(layers, n_layers, blob, blob_len, in_h, in_w, in_c, precision, &m);
+    if (rc == AA_OK) *model = m;
+    return rc;
+}
+
 extern "C" int aa_model_create(const aa_layer* layers, int32_t n_layers, const float* blob, int64_t blob_len,
                                int32_t in_h, int32_t in_w, int32_t in_c, int32_t precision, void** model) {
-    AA_CHECK(layers && blob && model && n_layers > 0, AA_ERR_INVALID, "aa_model_create: null argument");
-    AA_CHECK(precision == AA_PREC_F32 || precision == AA_PREC_BF16 || precision == AA_PREC_FP8 ||
-                 precision == AA_PREC_BF16X3, AA_ERR_INVALID,
-             "aa_model_create: precision %d", precision);
-    auto get = [&](int64_t off, int64_t n) -> const float* {
-        if (off < 0 || off + n > blob_len) return nullptr;
-        return blob + off;
-    };
-    Model* m = new Model();
-    m->prec = precision;
-    m->in_h = in_h;
-    m->in_w = in_w;
-    m->in_c = in_c;
-    int H = in_h, W = in_w, C = in_c;
-    int has_mag = 0;
-    float mag_exp = 1.f;
-    int i = 0;
-    int rc = AA_OK;
-    auto fail = [&](int code, const char* msg) {
-        set_error("aa_model_create: layer %d: %s", i, msg);
-        rc = code;
-    };
-    auto upload = [&](Stage& s, const void* w, size_t wbytes, const std::vector<float>& bias) -> bool {
-        hipError_t e = hipMalloc(&s.d_w, wbytes ? wbytes : 4);
-        if (e == hipSuccess && wbytes) e = hipMemcpy(s.d_w, w, wbytes, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMalloc((void**)&s.d_b, sizeof(float) * std::max<size_t>(bias.size(), 1));
-        if (e == hipSuccess && !bias.empty())
-            e = hipMemcpy(s.d_b, bias.data(), sizeof(float) * bias.size(), hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            m->st.push_back(s);
-            fail(AA_ERR_HIP, hipGetErrorString(e));
-            return false;
-        }
-        return true;
-    };
-    while (i < n_layers && rc == AA_OK) {
-        const aa_layer& ly = layers[i];
-        if (ly.op == AA_OP_MAGTRANSFORM) {
-            const float* a = get(ly.off[0], 1);
-            if (!a || !m->st.empty()) { fail(AA_ERR_UNSUPPORTED, "MagTransform must precede the first conv"); break; }
-            has_mag = 1;
-            mag_exp = 1.f / (1.f + expf(-a[0]));  // sigmoid(a) in f32 like tf.math.sigmoid
-            ++i;
-            continue;
-        }
-        if (ly.op == AA_OP_GLOBALMAXPOOL2D) {
-            // GlobalMaxPool2D [+ Dense] [+ sigmoid] after a conv stage: one
-            // pool_dense launch (the 1x1-conv head pattern is folded below)
-            if (m->st.empty()) { fail(AA_ERR_UNSUPPORTED, "GlobalMaxPool2D before any conv"); break; }
-            Stage s;
-            s.kind = ST_POOLDENSE;
-            s.Hin = H;
-            s.Win = W;
-            s.cin = C;
-            s.cout = C;
-            ++i;
-            std::vector<float> wd, bias;
-            if (i < n_layers && layers[i].op == AA_OP_DENSE) {
-                const aa_layer& d = layers[i];
-                s.cout = d.filters;
-                const float* k = get(d.off[0], (int64_t)C * d.filters);
-                if (!k || d.filters <= 0) { fail(AA_ERR_INVALID, "dense kernel outside the blob"); break; }
-                wd.assign(k, k + (size_t)C * d.filters);
-                bias.assign(d.filters, 0.f);
-                if (d.off[1] >= 0) {
-                    const float* bb = get(d.off[1], d.filters);
-                    if (!bb) { fail(AA_ERR_INVALID, "dense bias outside the blob"); break; }
-                    bias.assign(bb, bb + d.filters);
-                }
-                ++i;
-            }
-            if (i < n_layers && layers[i].op == AA_OP_SIGMOID) {
-                s.sigmoid = 1;
-                ++i;
-            }
-            if (i != n_layers) { fail(AA_ERR_UNSUPPORTED, "layers after the global pooling / dense"); break; }
-            s.cout_pad = s.cout;
-            if (!upload(s, wd.empty() ? nullptr : wd.data(), wd.size() * sizeof(float), bias)) break;
-            if (wd.empty()) {  // no Dense: pool_dense reads a null weight pointer
-                (void)hipFree(s.d_w);
-                s.d_w = nullptr;
-            }
-            s.flops = 2.0 * C * (wd.empty() ? 0 : s.cout);
-            s.bytes = (double)prec_bytes(precision) * H * W * C + 4.0 * s.cout;
-            char nm[96];
-            snprintf(nm, sizeof nm, "globalmax%s_%d_%d", wd.empty() ? "" : "_dense", C, s.cout);
-            s.name = nm;
-            m->st.push_back(s);
-            m->L = s.cout;
-            continue;
-        }
-        if (ly.op != AA_OP_CONV2D) { fail(AA_ERR_UNSUPPORTED, "expected Conv2D"); break; }
-        Stage s;
-        s.kh = ly.kh;
-        s.kw = ly.kw;
-        s.cin = C;
-        s.cout = ly.filters;
-        s.Hin = H;
-        s.Win = W;
-        s.Hc = H - ly.kh + 1;
-        s.Wc = W - ly.kw + 1;
-        s.is_first = m->st.empty();
-        if (s.Hc <= 0 || s.Wc <= 0) { fail(AA_ERR_INVALID, "input smaller than the kernel"); break; }
-        const int K = s.kh * s.kw * s.cin;
-        const float* kern = get(ly.off[0], (int64_t)K * s.cout);
-        if (!kern) { fail(AA_ERR_INVALID, "conv kernel outside the blob"); break; }
-        std::vector<double> scale(s.cout, 1.0), shift(s.cout, 0.0);
-        if (ly.off[1] >= 0) {
-            const float* b = get(ly.off[1], s.cout);
-            if (!b) { fail(AA_ERR_INVALID, "bias outside the blob"); break; }
-            for (int c = 0; c < s.cout; ++c) shift[c] = b[c];
-        }
-        ++i;
-        // absorb BN / activation / pool / head
-        if (i < n_layers && layers[i].op == AA_OP_BATCHNORM) {
-            const aa_layer& bn = layers[i];
-            const float *g = get(bn.off[0], s.cout), *be = get(bn.off[1], s.cout), *mu = get(bn.off[2], s.cout),
-                        *var = get(bn.off[3], s.cout);
-            if (!g || !be || !mu || !var) { fail(AA_ERR_INVALID, "batchnorm params outside the blob"); break; }
-            for (int c = 0; c < s.cout; ++c) {
-                const double sc = (double)g[c] / std::sqrt((double)var[c] + (double)bn.eps);
-                shift[c] = (shift[c] - mu[c]) * sc + be[c];
-                scale[c] = sc;
-            }
-            ++i;
-        }
-        if (i < n_layers && (layers[i].op == AA_OP_LEAKYRELU || layers[i].op == AA_OP_RELU)) {
-            s.act = layers[i].op == AA_OP_LEAKYRELU ? ACT_LEAKY : ACT_RELU;
-            s.alpha = layers[i].alpha;
-            if (s.act == ACT_LEAKY && s.alpha < 0.f) { fail(AA_ERR_UNSUPPORTED, "LeakyReLU with a negative slope"); break; }
-            ++i;
-        }
-        if (i < n_layers && layers[i].op == AA_OP_MAXPOOL2D) {
-            if (layers[i].kh <= 0 || layers[i].kw <= 0) { fail(AA_ERR_INVALID, "max-pool window"); break; }
-            s.ph = layers[i].kh;
-            s.pw = layers[i].kw;
-            ++i;
-        }
-        s.pool = (s.ph == s.pw && (s.ph == 1 || s.ph == 3)) ? s.ph : 0;
-        s.Hout = s.Hc / s.ph;
-        s.Wout = s.Wc / s.pw;
-        if (s.Hout <= 0 || s.Wout <= 0) { fail(AA_ERR_INVALID, "pool window larger than the conv output"); break; }
-        const bool gpool = i < n_layers && layers[i].op == AA_OP_GLOBALMAXPOOL2D;
-        const bool dense_next = gpool && i + 1 < n_layers && layers[i + 1].op == AA_OP_DENSE;
-        // (the first stage reads the f32 model input: only ST_SMALL / ST_GENERIC do)
-        if (!s.is_first && gpool && !dense_next && s.kh == 1 && s.kw == 1 && s.ph == 1 && s.pw == 1 &&
-            s.cin % 32 == 0 && s.cout <= 1024) {
-            // the reference family's head: 1x1 conv, global max, sigmoid
-            s.kind = ST_HEAD;
-            ++i;
-            if (i < n_layers && layers[i].op == AA_OP_SIGMOID) {
-                s.sigmoid = 1;
-                ++i;
-            }
-            if (i != n_layers) { fail(AA_ERR_UNSUPPORTED, "layers after the 1x1 head"); break; }
-        } else if (s.cin == 1 && s.kh == 3 && s.kw == 3 && s.cout == 32 && s.pool == 1) {
-            s.kind = ST_SMALL;
-        } else if (!s.is_first && s.pool && mfma_bn(precision, s.kh, s.kw, s.cin, s.pool)) {
-            s.kind = ST_MFMA;
-        } else if (precision == AA_PREC_BF16X3 && !s.is_first && s.cin >= 16) {
-            s.kind = ST_GCONV;  // any other shape with a real contraction: the runtime-shaped MFMA kernel
-        } else {
-            s.kind = ST_GENERIC;
-            if (precision == AA_PREC_FP8) {
-                fail(AA_ERR_UNSUPPORTED, "no fp8 kernel for this conv shape (the f32 / bf16x3 / bf16 modes have one)");
-                break;
-            }
-        }
-        if (s.is_first) {
-            s.has_mag = has_mag;
-            s.mag_exp = mag_exp;
-            if (has_mag && s.kind != ST_SMALL && s.kind != ST_GENERIC) {
-                fail(AA_ERR_UNSUPPORTED, "MagTransform needs a C_in=1 first conv");
-                break;
-            }
-        }
-        int bn_tile = 32;
-        if (s.kind == ST_MFMA) bn_tile = mfma_bn(precision, s.kh, s.kw, s.cin, s.pool);
-        if (s.kind == ST_GCONV) {
-            // [tap][cin_pad / 32][cout_pad][32 hi | 32 lo], BN folded (aa_gconv.h)
-            s.cout_pad = (s.cout + 63) / 64 * 64;
-            s.cin_pad = (s.cin + 31) / 32 * 32;
-            const int ntap = s.kh * s.kw;
-            std::vector<float> w_tco((size_t)ntap * s.cout * s.cin);
-            for (int t = 0; t < ntap; ++t)
-                for (int o = 0; o < s.cout; ++o)
-                    for (int c = 0; c < s.cin; ++c)
-                        w_tco[((size_t)t * s.cout + o) * s.cin + c] =
-                            (float)(kern[((size_t)t * s.cin + c) * s.cout + o] * scale[o]);
-            const std::vector<uint16_t> h = gconv_pack_x3(w_tco, ntap, s.cout, s.cin, s.cout_pad, s.cin_pad);
-            std::vector<float> bias(s.cout_pad, 0.f);
-            for (int o = 0; o < s.cout; ++o) bias[o] = (float)shift[o];
-            if (!upload(s, h.data(), h.size() * 2, bias)) break;
-            s.flops = 2.0 * s.Hc * s.Wc * K * s.cout;
-            s.bytes = 4.0 * s.Hin * s.Win * s.cin + 4.0 * s.Hout * s.Wout * s.cout;
-            char nm[96], pl[24] = "";
-            if (s.ph > 1 || s.pw > 1) snprintf(pl, sizeof pl, s.ph == s.pw ? "_pool%d" : "_pool%dx%d", s.ph, s.pw);
-            snprintf(nm, sizeof nm, "conv_gx3_%dx%d_%d_%d%s", s.kh, s.kw, s.cin, s.cout, pl);
-            s.name = nm;
-            if (s.ph > 1 || s.pw > 1) m->tmp_elems = std::max(m->tmp_elems, (size_t)s.Hc * s.Wc * s.cout);
-            m->st.push_back(s);
-            H = s.Hout;
-            W = s.Wout;
-            C = s.cout;
-            continue;
-        }
-        s.wg = 0;
-        if (precision == AA_PREC_BF16X3 && s.kind == ST_MFMA && wg_bn(s.kh, s.kw, s.cin, s.pool) > 0)
-            wg_form(s.kh, s.cin, s.pool, &s.wg, &s.wg_npass);
-        const bool rowmajor = s.kind == ST_SMALL || s.kind == ST_GENERIC;  // f32 [cout][K]
-        s.cout_pad = rowmajor ? s.cout : (s.cout + bn_tile - 1) / bn_tile * bn_tile;
-        // pack weights with the BN scale folded in: conv_small / generic
-        // [cout][K] f32; MFMA stages tap-major with padded rows
-        // [kh*KW + kw][cout_pad][cstr] (a block's per-tap slice is one
-        // contiguous block, byte-identical to its LDS image) plus 1 KiB of
-        // slack for the last slice's rounding; the 1x1 head [cout_pad][C_in]
-        const bool bf = (precision == AA_PREC_BF16) && !rowmajor;
-        const bool f8 = (precision == AA_PREC_FP8) && !rowmajor;
-        // split-bf16: conv_x3 steps of hi/lo bf16 rows (packed below from the
-        // compact f32 [tap][cout_pad][C_in] image); the head stays f32
-        const bool sp = (precision == AA_PREC_BF16X3) && s.kind == ST_MFMA;
-        const int wes = (bf || sp) ? 2 : f8 ? 1 : 4;
-        const int cstr = s.kind == ST_MFMA ? (bf ? conv_cstr<bf16>(s.cin) : f8 ? conv_cstr<fp8>(s.cin)
-                                              : sp ? s.cin : conv_cstr<float>(s.cin))
-                                           : s.cin;
-        const int ntap = s.kh * s.kw;
-        const size_t slack = s.kind == ST_MFMA ? 1024 / wes : 0;
-        std::vector<float> wpk(rowmajor ? (size_t)s.cout * K : (size_t)ntap * s.cout_pad * cstr + slack, 0.f);
-        for (int o = 0; o < s.cout; ++o)
-            for (int k = 0; k < K; ++k) {
-                const double v = kern[(size_t)k * s.cout + o] * scale[o];
-                if (rowmajor) {
-                    wpk[(size_t)o * K + k] = (float)v;
-                } else {
-                    const int t = k / s.cin, c = k - t * s.cin;
-                    wpk[((size_t)t * s.cout_pad + o) * cstr + c] = (float)v;
-                }
-            }
-        // fp8: [bias | per-channel dequantisation scale], both cout_pad long
-        std::vector<float> bias(f8 ? 2 * s.cout_pad : s.cout_pad, 0.f);
-        for (int o = 0; o < s.cout; ++o) bias[o] = (float)shift[o];
-        // split-bf16 stores hi + lo: twice the compact image's elements
-        const size_t wbytes = (sp ? 2 * wpk.size() : wpk.size()) * wes;
-        bool ok = true;
-        if (f8) {
-            // per output channel: the largest |w| maps to 240 (e4m3fn tops
-            // out at 448), the kernel's epilogue multiplies by amax / 240.
-            // conv stages: super-steps of four 32-channel chunks (chunk k =
-            // tap k / (C_in/32), channels 32 (k % (C_in/32)) ..), each
-            // [cout_pad][F8_BSTR] with chunk k % 4 at byte 32 (k % 4) of the
-            // row (conv_mfma's K = 128 loop); the head keeps [cout_pad][cstr]
-            const bool ss = s.kind == ST_MFMA && conv_k128<fp8>(s.cin);
-            const int cpc = s.cin / 32, nch = ntap * cpc, nss = conv_nstep<fp8>(ntap, s.cin);
-            std::vector<uint8_t> h(ss ? (size_t)nss * s.cout_pad * F8_BSTR + 1024 : wpk.size(), 0);
-            for (int o = 0; o < s.cout_pad; ++o) {
-                float amax = 0.f;
-                for (int t = 0; t < ntap; ++t)
-                    for (int c = 0; c < s.cin; ++c) amax = std::max(amax, std::fabs(wpk[((size_t)t * s.cout_pad + o) * cstr + c]));
-                const float sc = amax > 0.f ? 240.f / amax : 1.f;
-                bias[s.cout_pad + o] = 1.f / sc;
-                if (ss) {
-                    for (int k = 0; k < nch; ++k)
-                        for (int c = 0; c < 32; ++c) {
-                            const int t = k / cpc, cc = k % cpc;
-                            h[((size_t)(k / 4) * s.cout_pad + o) * F8_BSTR + 32 * (k % 4) + c] =
-                                f2fp8(wpk[((size_t)t * s.cout_pad + o) * cstr + 32 * cc + c] * sc);
-                        }
-                } else {
-                    for (int t = 0; t < ntap; ++t)
-                        for (int c = 0; c < s.cin; ++c) {
-                            const size_t k = ((size_t)t * s.cout_pad + o) * cstr + c;
-                            h[k] = f2fp8(wpk[k] * sc);
-                        }
-                }
-            }
-            ok = upload(s, h.data(), h.size(), bias);
-        } else if (bf) {
-            std::vector<uint16_t> h(wpk.size());
-            for (size_t k = 0; k < wpk.size(); ++k) h[k] = f2bf(wpk[k]);
-            ok = upload(s, h.data(), wbytes, bias);
-        } else if (sp) {
-            // conv_x3 steps (32-channel group g, tap t) in order s = g * ntap + t,
-            // each [cout_pad][8 units of 8 bf16]: units 0-3 hi = rn_bf16(w) of
-            // channels 32 g + 8 u .. + 7, units 4-7 lo = rn_bf16(w - hi), unit u
-            // of row o stored in slot (u + o) & 7 (aa_conv_x3.h)
-            std::vector<uint16_t> h(2 * wpk.size(), 0);
-            const int ng = s.cin / 32;
-            if (s.wg) {
-                // conv_wg steps (group g, pass p, row kh, plane slot el) in order
-                // ((g * npass + p) * kh + kh) * pps + el, each [cout_pad][8 units] as
-                // above, holding the transformed weights v_e = sum_k G[e][k] w_k of
-                // plane e = p * pps + el (w_kw = the folded kernel at (kh, kw);
-                // F(2,3): v0 = w0, v1 = (w0 + w1 + w2) / 2, v2 = (w0 - w1 + w2) / 2,
-                // v3 = w2), computed in double
-                const int A = s.wg + 2, np = s.wg_npass, pps = A / np;
-                h.assign((size_t)ng * s.kh * A * s.cout_pad * 64 * 2 + 1024, 0);
-                for (int g = 0; g < ng; ++g)
-                    for (int kh = 0; kh < s.kh; ++kh)
-                        for (int o = 0; o < s.cout_pad; ++o)
-                            for (int c = 0; c < 32; ++c) {
-                                double w3[3];
-                                for (int kw = 0; kw < 3; ++kw)
-                                    w3[kw] = o < s.cout ? (double)kern[((size_t)(kh * 3 + kw) * s.cin + 32 * g + c) * s.cout + o] * scale[o] : 0.0;
-                                for (int e = 0; e < A; ++e) {
-                                    const double v = wg_g(s.wg, e, 0) * w3[0] + wg_g(s.wg, e, 1) * w3[1] + wg_g(s.wg, e, 2) * w3[2];
-                                    const int p = e / pps, el = e % pps;
-                                    const size_t row = ((size_t)(((g * np + p) * s.kh + kh) * pps + el) * s.cout_pad + o) * 64;
-                                    const float w = (float)v;
-                                    const uint16_t hi = f2bf(w);
-                                    const int u = c / 8;
-                                    h[row + ((u + o) & 7) * 8 + c % 8] = hi;
-                                    h[row + ((u + 4 + o) & 7) * 8 + c % 8] = f2bf(w - bf2f(hi));
-                                }
-                            }
-                ok = upload(s, h.data(), h.size() * 2, bias);
-            } else {
-            for (int g = 0; g < ng; ++g)
-                for (int t = 0; t < ntap; ++t)
-                    for (int o = 0; o < s.cout_pad; ++o) {
-                        const size_t row = ((size_t)(g * ntap + t) * s.cout_pad + o) * 64;
-                        for (int c = 0; c < 32; ++c) {
-                            const float w = wpk[((size_t)t * s.cout_pad + o) * cstr + 32 * g + c];
-                            const uint16_t hi = f2bf(w);
-                            const int u = c / 8;
-                            h[row + ((u + o) & 7) * 8 + c % 8] = hi;
-                            h[row + ((u + 4 + o) & 7) * 8 + c % 8] = f2bf(w - bf2f(hi));
-                        }
-                    }
-            ok = upload(s, h.data(), wbytes, bias);
-            }
-        } else {
-            ok = upload(s, wpk.data(), wbytes, bias);
-        }
-        if (!ok) break;
-        s.flops = 2.0 * s.Hc * s.Wc * K * s.cout;
-        const double es = (double)prec_bytes(precision);
-        s.bytes = (s.is_first ? 4.0 : es) * s.Hin * s.Win * s.cin +
-                  (s.kind == ST_HEAD ? 4.0 * s.cout : es * s.Hout * s.Wout * s.cout);
-        char nm[96], pl[24] = "";
-        if (s.ph > 1 || s.pw > 1) snprintf(pl, sizeof pl, s.ph == s.pw ? "_pool%d" : "_pool%dx%d", s.ph, s.pw);
-        snprintf(nm, sizeof nm, "%s%dx%d_%d_%d%s",
-                 s.kind == ST_SMALL ? "conv_small_" : s.kind == ST_HEAD ? "head_" : s.kind == ST_GENERIC ? "conv_generic_" : "conv_",
-                 s.kh, s.kw, s.cin, s.cout, pl);
-        s.name = nm;
-        m->st.push_back(s);
-        H = s.Hout;
-        W = s.Wout;
-        C = s.cout;
-        if (s.kind == ST_HEAD) m->L = s.cout;
-    }
-    if (rc == AA_OK && (m->st.empty() || (m->st.back().kind != ST_HEAD && m->st.back().kind != ST_POOLDENSE))) {
-        set_error("aa_model_create: the model must end with GlobalMaxPool2D (after a 1x1 conv or before a Dense)");
-        rc = AA_ERR_UNSUPPORTED;
-    }
+    void* m = nullptr;
+    int rc = aa_model_plan(layers, n_layers, blob, blob_len, in_h, in_w, in_c, precision, model ? &m : nullptr);
+    if (rc != AA_OK) return rc;
+    rc = upload_model(static_cast<Model*>(m));
     if (rc != AA_OK) {
-        free_model(m);
+        free_model(static_cast<Model*>(m));
         return rc;
     }
-    // fuse a C_in = 1 first conv (3x3 -> 32) into the following 3x3/32 pooled conv
-    if (m->st.size() >= 2 && fusable_first(m->st[0], m->st[1])) {
-        m->st[0].skipped = 1;
-        m->st[1].fused_first = 1;
-        m->st[1].flops += m->st[0].flops;
-        // the fused pair reads the first conv's f32 input and writes the
-        // second's output; the first conv's activations never reach HBM
-        const double es1 = (double)prec_bytes(precision);
-        m->st[1].bytes = 4.0 * m->st[0].Hin * m->st[0].Win * m->st[0].cin +
-                         (m->st[1].bytes - es1 * m->st[1].Hin * m->st[1].Win * m->st[1].cin);
-        m->st[1].name = m->st[0].name + "+" + m->st[1].name;
-    }
-    // split-bf16: a conv_x3 stage whose consumer is another conv_x3 stage
-    // writes the grouped-split layout, and that consumer stages it by
-    // global_load_lds alone (aa_conv_x3.h); heads / generic stages keep f32
-    if (precision == AA_PREC_BF16X3) {
-        for (size_t k = 0; k + 1 < m->st.size(); ++k) {
-            Stage& a = m->st[k];
-            Stage& b = m->st[k + 1];
-            if (a.skipped || a.kind != ST_MFMA || b.kind != ST_MFMA || b.fused_first) continue;
-            if (a.cout % 32 != 0 || b.cin != a.cout) continue;
-            // a Winograd consumer transforms f32 values before it splits them: it
-            // reads plain f32 (one 16-B load per 4 channels, not two 8-B loads and
-            // a hi + lo sum); the split layout only pays for global_load_lds staging
-            if (b.wg) continue;
-            a.out_split = 1;
-            b.in_split = 1;
-        }
-    }
-    // split-bf16: the 1x3/128 -> 256 conv before a 1x1 head (<= 32 labels) and
-    // the head in one kernel (aa_conv_tail.h); the conv's 13 x 20 x 256
-    // activations never reach HBM.
-    if (precision == AA_PREC_BF16X3 && m->st.size() >= 2) {
-        Stage& h = m->st.back();
-        Stage& c = m->st[m->st.size() - 2];
-        if (h.kind == ST_HEAD && h.cout <= 32 && h.cout_pad == 32 && h.cin == 256 && c.kind == ST_MFMA && !c.skipped &&
-            !c.fused_first && !c.wg && c.in_split && !c.out_split && c.kh == 1 && c.kw == 3 && c.cin == 128 &&
-            c.cout == 256 && c.cout_pad == 256 && c.pool == 1 && c.ph == 1 && c.pw == 1) {
-            // head weights f32 [cout_pad][256] -> per (wave w, label fragment lf,
-            // hi / lo, lane l) 8 bf16: label 16 lf + (l & 15), k-slot e <-> channel
-            // 32 w + (e < 4 ? 4 (l >> 4) + e : 16 + 4 (l >> 4) + e - 4)
-            std::vector<float> hwf((size_t)h.cout_pad * h.cin);
-            hipError_t e = hipMemcpy(hwf.data(), h.d_w, hwf.size() * 4, hipMemcpyDeviceToHost);
-            std::vector<uint16_t> pk((size_t)TAIL_NW * 2 * 2 * 64 * 8, 0);
-            for (int w = 0; w < TAIL_NW; ++w)
-                for (int lf = 0; lf < 2; ++lf)
-                    for (int l = 0; l < 64; ++l)
-                        for (int k = 0; k < 8; ++k) {
-                            const int lab = lf * 16 + (l & 15), qq = l >> 4;
-                            const int co = 32 * w + (k < 4 ? 4 * qq + k : 16 + 4 * qq + k - 4);
-                            const float v = lab < h.cout ? hwf[(size_t)lab * h.cin + co] : 0.f;
-                            const uint16_t hi = f2bf(v);
-                            pk[((((size_t)w * 2 + lf) * 2 + 0) * 64 + l) * 8 + k] = hi;
-                            pk[((((size_t)w * 2 + lf) * 2 + 1) * 64 + l) * 8 + k] = f2bf(v - bf2f(hi));
-                        }
-            if (e == hipSuccess) e = hipMalloc(&h.d_tw, pk.size() * 2);
-            if (e == hipSuccess) e = hipMemcpy(h.d_tw, pk.data(), pk.size() * 2, hipMemcpyHostToDevice);
-            if (e != hipSuccess) {
-                set_error("aa_model_create: %s", hipGetErrorString(e));
-                free_model(m);
-                return AA_ERR_HIP;
-            }
-            c.skipped = 1;
-            h.tail = 1;
-            h.flops += c.flops;
-            h.bytes = 4.0 * c.Hin * c.Win * c.cin + 4.0 * h.cout;
-            h.name = c.name + "+" + h.name;
-        }
-    }
-    // ping-pong activation buffers: stage s writes buffer s % 2
-    for (size_t k = 0; k + 1 < m->st.size(); ++k) {
-        const Stage& s = m->st[k];
-        if (s.skipped || s.kind == ST_POOLDENSE) continue;
-        const size_t e = (size_t)s.Hout * s.Wout * s.cout;
-        m->act_elems[k % 2] = std::max(m->act_elems[k % 2], e);
-    }
-    if (!m->st.empty() && m->st.back().kind == ST_HEAD) {  // the head's partial maxima use its free buffer
-        const Stage& h = m->st.back();
-        const size_t es = prec_bytes(precision);
-        const size_t parts = ((size_t)h.Hin * h.Win + 63) / 64;
-        const size_t k = m->st.size() - 1;
-        m->act_elems[k % 2] = std::max(m->act_elems[k % 2], (parts * h.cout_pad * sizeof(float) + es - 1) / es);
-        if (h.tail) {  // the fused tail's per-tile maxima go to the skipped conv stage's buffer
-            const Stage& c = m->st[k - 1];
-            const size_t tiles = (size_t)((c.Hc + 12) / 13) * ((c.Wc + 4) / 5);
-            m->act_elems[(k - 1) % 2] = std::max(m->act_elems[(k - 1) % 2], (tiles * 32 * sizeof(float) + es - 1) / es);
-        }
-    }
     *model = m;
+    return AA_OK;
+}
+
+extern "C" int aa_model_stage_image(const void* model, int32_t stage, int32_t which, void* buf, size_t cap,
+                                    size_t* len) {
+    const Model* m = static_cast<const Model*>(model);
+    AA_CHECK(m && len && stage >= 0 && stage < (int)m->st.size() && which >= 0 && which <= 2, AA_ERR_INVALID,
+             "aa_model_stage_image: bad argument");
+    AA_CHECK(!m->uploaded, AA_ERR_UNSUPPORTED,
+             "aa_model_stage_image: the host images are released once a model is created; plan it (aa_model_plan)");
+    const Stage& s = m->st[stage];
+    const void* src = which == 0 ? (const void*)s.h_w.data() : which == 1 ? (const void*)s.h_b.data() : s.h_tw.data();
+    *len = which == 0 ? s.h_w.size() : which == 1 ? s.h_b.size() * sizeof(float) : s.h_tw.size();
+    if (!buf) return AA_OK;  // a size query
+    AA_CHECK(cap >= *len, AA_ERR_INVALID, "aa_model_stage_image: buffer %zu < %zu", cap, *len);
+    if (*len) memcpy(buf, src, *len);
     return AA_OK;
 }
 
@@ -2033,6 +1504,7 @@ extern "C" size_t aa_model_workspace_bytes(const void* model, int32_t max_batch)
 extern "C" int aa_model_set_input_f16(void* model, int32_t f16) {
     Model* m = static_cast<Model*>(model);
     AA_CHECK(m && (f16 == 0 || f16 == 1), AA_ERR_INVALID, "aa_model_set_input_f16: bad argument");
+    AA_CHECK(m->uploaded, AA_ERR_INVALID, "aa_model_set_input_f16: the model is a plan (aa_model_plan), not created");
     AA_CHECK(!f16 || (m->st.size() >= 2 && m->st[1].fused_first), AA_ERR_UNSUPPORTED,
              "aa_model_set_input_f16: float16 input needs the fused first conv (3x3 C_in=1 -> 32 before a "
              "pooled 3x3/32 conv)");
@@ -2044,15 +1516,11 @@ extern "C" int aa_model_forward(void* model, const void* x, int32_t n, float* lo
                                 void* workspace, size_t workspace_bytes, void* stream) {
     Model* m = static_cast<Model*>(model);
     AA_CHECK(m && x && logits, AA_ERR_INVALID, "aa_model_forward: null argument");
+    AA_CHECK(m->uploaded, AA_ERR_INVALID, "aa_model_forward: the model is a plan (aa_model_plan), not created");
     if (n <= 0) return AA_OK;
     const size_t need = aa_model_workspace_bytes(m, n);
     AA_CHECK(workspace && workspace_bytes >= need, AA_ERR_WORKSPACE, "aa_model_forward: workspace %zu < %zu",
              workspace_bytes, need);
-    const size_t es = prec_bytes(m->prec);
-    char* buf[2] = {static_cast<char*>(workspace),
-                    static_cast<char*>(workspace) + align_up(m->act_elems[0] * es * n, 256)};
-    float* tmp = reinterpret_cast<float*>(buf[1] + align_up(m->act_elems[1] * es * n, 256));
-    hipStream_t st = static_cast<hipStream_t>(stream);
     // launch grids carry the window index in blockIdx.z (at most 65,535):
     // larger batches run as consecutive chunks through the same workspace
     constexpr int32_t CHUNK = 32768;
@@ -2068,27 +1536,7 @@ extern "C" int aa_model_forward(void* model, const void* x, int32_t n, float* lo
         }
         return AA_OK;
     }
-    const void* in = x;
-    for (size_t k = 0; k < m->st.size(); ++k) {
-        Stage& s = m->st[k];
-        if (s.skipped) continue;  // computed inside stage k + 1 (reads x directly)
-        // (a fused tail writes its per-tile maxima into the skipped conv stage's
-        // buffer: its own would be the one its input lives in)
-        void* out = buf[(s.tail ? k - 1 : k) % 2];
-        const Stage* first = (s.fused_first || s.tail) ? &m->st[k - 1] : nullptr;
-        hipEvent_t e0;
-        int rc = m->timer.begin((int)k, st, &e0);
-        if (rc != AA_OK) return rc;
-        rc = m->prec == AA_PREC_BF16     ? launch_stage<bf16>(*m, s, in, out, logits, probs, n, st, first, tmp)
-             : m->prec == AA_PREC_FP8    ? launch_stage<fp8>(*m, s, in, out, logits, probs, n, st, first, tmp)
-             : m->prec == AA_PREC_BF16X3 ? launch_stage<bf16x3>(*m, s, in, out, logits, probs, n, st, first, tmp)
-                                         : launch_stage<float>(*m, s, in, out, logits, probs, n, st, first, tmp);
-        if (rc != AA_OK) return rc;
-        rc = m->timer.end((int)k, st, e0);
-        if (rc != AA_OK) return rc;
-        in = out;
-    }
-    return AA_OK;
+    return run_stages(m, x, n, (int)m->st.size() - 1, logits, probs, workspace, static_cast<hipStream_t>(stream), true);
 }
 
 extern "C" int aa_model_n_stages(const void* model) {
@@ -2139,6 +1587,7 @@ extern "C" int aa_model_forward_prefix(void* model, const void* x, int32_t n, in
                                        void* workspace, size_t workspace_bytes, void* stream) {
     Model* m = static_cast<Model*>(model);
     AA_CHECK(m && x && act, AA_ERR_INVALID, "aa_model_forward_prefix: null argument");
+    AA_CHECK(m->uploaded, AA_ERR_INVALID, "aa_model_forward_prefix: the model is a plan (aa_model_plan), not created");
     int32_t sh, sw, sc;
     const int src = aa_model_stage_shape(model, stage, &sh, &sw, &sc);
     if (src != AA_OK) return src;
@@ -2147,31 +1596,15 @@ extern "C" int aa_model_forward_prefix(void* model, const void* x, int32_t n, in
     const size_t need = aa_model_workspace_bytes(m, n);
     AA_CHECK(workspace && workspace_bytes >= need, AA_ERR_WORKSPACE, "aa_model_forward_prefix: workspace %zu < %zu",
              workspace_bytes, need);
-    // the buffers and the launches of aa_model_forward, stages 0..stage
-    const size_t es = prec_bytes(m->prec);
-    char* buf[2] = {static_cast<char*>(workspace),
-                    static_cast<char*>(workspace) + align_up(m->act_elems[0] * es * n, 256)};
-    float* tmp = reinterpret_cast<float*>(buf[1] + align_up(m->act_elems[1] * es * n, 256));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const void* in = x;
-    for (int32_t k = 0; k <= stage; ++k) {
-        const Stage& s = m->st[k];
-        if (s.skipped) continue;
-        void* out = buf[k % 2];
-        const Stage* first = s.fused_first ? &m->st[k - 1] : nullptr;
-        const int rc = m->prec == AA_PREC_BF16     ? launch_stage<bf16>(*m, s, in, out, nullptr, nullptr, n, st, first, tmp)
-                       : m->prec == AA_PREC_FP8    ? launch_stage<fp8>(*m, s, in, out, nullptr, nullptr, n, st, first, tmp)
-                       : m->prec == AA_PREC_BF16X3 ? launch_stage<bf16x3>(*m, s, in, out, nullptr, nullptr, n, st, first, tmp)
-                                                   : launch_stage<float>(*m, s, in, out, nullptr, nullptr, n, st, first, tmp);
-        if (rc != AA_OK) return rc;
-        in = out;
-    }
-    const Stage& s = m->st[stage];
+    const void* in = nullptr;
+    const int rc = run_stages(m, x, n, stage, nullptr, nullptr, workspace, st, false, &in);
+    if (rc != AA_OK) return rc;
     const size_t total = (size_t)n * sh * sw * sc;
     const unsigned blocks = (unsigned)std::min<size_t>((total + 255) / 256, 65536);
     // ST_SMALL / ST_GENERIC / ST_GCONV store the mode's plain activation type;
     // only a conv_x3 / conv_wg stage with out_split writes the grouped split
-    if (s.out_split)
+    if (m->st[stage].out_split)
         hipLaunchKernelGGL(stage_decode<3>, dim3(blocks), dim3(256), 0, st, in, act, total, sc);
     else if (m->prec == AA_PREC_BF16)
         hipLaunchKernelGGL(stage_decode<1>, dim3(blocks), dim3(256), 0, st, in, act, total, sc);

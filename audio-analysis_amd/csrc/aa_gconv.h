@@ -814,35 +814,6 @@ static __global__ __launch_bounds__(256) void gpool2d(const float* __restrict__ 
     out[(size_t)n * Hout * Wout * C + i] = gact(m, act, alpha);
 }
 
-// host: split-bf16 weight packing for gconv_x3 from a compact f32 [tap][Cout][Cin]
-// image (BN already folded): [tap][cin_pad/32][cout_pad][32 hi | 32 lo]
-static inline uint16_t g_f2bf(float f) {
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7fc0;
-    u += 0x7fff + ((u >> 16) & 1);
-    return (uint16_t)(u >> 16);
-}
-static inline float g_bf2f(uint16_t b) {
-    const uint32_t u = (uint32_t)b << 16;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
-static inline std::vector<uint16_t> gconv_pack_x3(const std::vector<float>& w_tco, int ntap, int cout, int cin,
-                                                  int cout_pad, int cin_pad) {
-    const int ncc = cin_pad / 32;
-    std::vector<uint16_t> h((size_t)ntap * ncc * cout_pad * 64, 0);
-    for (int t = 0; t < ntap; ++t)
-        for (int o = 0; o < cout; ++o)
-            for (int c = 0; c < cin; ++c) {
-                const float w = w_tco[((size_t)t * cout + o) * cin + c];
-                const uint16_t hi = g_f2bf(w);
-                const size_t row = ((size_t)(t * ncc + c / 32) * cout_pad + o) * 64;
-                h[row + c % 32] = hi;
-                h[row + 32 + c % 32] = g_f2bf(w - g_bf2f(hi));
-            }
-    return h;
-}
+// (host: gconv_x3's split-bf16 weight packing is gconv_pack_x3, aa_cnn_pack.h)
 
 }  // namespace aa

@@ -25,6 +25,7 @@
 #include <string>
 
 #include "aa_common.h"
+#include "aa_cnn_pack.h"
 #include "aa_gconv.h"
 
 namespace aa {

@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define AA_ABI_VERSION 3
+#define AA_ABI_VERSION 4
 
 typedef enum aa_status {
     AA_OK = 0,
@@ -194,6 +194,23 @@ int aa_model_stage_time(void* model, int32_t stage, double* total_ms, int64_t* c
 int aa_model_stage_shape(const void* model, int32_t stage, int32_t* h, int32_t* w, int32_t* c);
 int aa_model_forward_prefix(void* model, const void* x, int32_t n, int32_t stage, float* act,
                             void* workspace, size_t workspace_bytes, void* stream);
+
+/* The plan alone, on the host: aa_model_create's arguments, checks, return
+ * codes and aa_last_error texts, but no device memory and no HIP call, so it
+ * runs on a machine without a GPU.  aa_model_n_stages / stage_info /
+ * stage_shape / n_outputs / workspace_bytes / destroy serve a planned model;
+ * aa_model_forward, aa_model_forward_prefix and aa_model_set_input_f16
+ * return AA_ERR_INVALID.
+ * stage_image copies out the bytes aa_model_create would upload for a stage:
+ * which = 0 the packed weights (len 0: the stage reads a null pointer), 1 the
+ * bias (fp8: followed by the dequantisation scales), 2 the fused tail's head
+ * weights (len 0 unless the stage is the fused tail).  *len: the image's
+ * bytes; buf NULL: size query; AA_ERR_INVALID when cap < *len.  Planned
+ * models only: a created model has released its host images
+ * (AA_ERR_UNSUPPORTED). */
+int aa_model_plan(const aa_layer* layers, int32_t n_layers, const float* blob, int64_t blob_len,
+                  int32_t in_h, int32_t in_w, int32_t in_c, int32_t precision, void** model);
+int aa_model_stage_image(const void* model, int32_t stage, int32_t which, void* buf, size_t cap, size_t* len);
 
 /* ---------------- CNN graphs (DAG models: residual / squeeze-excite / depthwise) ---------------- */
 /* Models that are not a single conv chain -- Keras Functional graphs such as

@@ -68,7 +68,7 @@ def _rows(macro, text):
 
 
 def tiles_from_sources():
-    text = (CSRC / "aa_cnn.hip").read_text()
+    text = (CSRC / "aa_cnn_tiles.h").read_text()
     out = {}
     for r in _rows("AA_X3_CFGS", text):  # KH, KW, CIN, POOL, WM, WN, MF, NF, TH, TW, RING, AJIT, OCC
         kh, kw, cin, pool, wm, wn, mf, nf, th, tw = (int(v) for v in r[:10])
@@ -80,7 +80,7 @@ def tiles_from_sources():
         prec = {"float": "f32", "bf16": "bf16", "fp8": "fp8"}[r[0]]
         kh, kw, cin, pool, wm, wn, mf, nf, th, tw = (int(v) for v in r[1:11])
         out[(prec, kh, kw, cin, pool)] = dict(TH=th, TW=tw, BN=wn * nf * 16, WO=0, EB={"true": True, "false": False}[r[11]])
-    th = re.search(r"constexpr int TH = (\d+), TW = AA_TAIL_TW;", text)
+    th = re.search(r"constexpr int TAIL_TH = (\d+), TAIL_TW = AA_TAIL_TW;", text)
     tw = re.search(r"#define AA_TAIL_TW (\d+)", text)
     assert th and tw
     return out, dict(TH=int(th.group(1)), TW=int(tw.group(1)))

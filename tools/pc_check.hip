@@ -34,18 +34,7 @@ int main(int argc, char** argv) {
     std::vector<uint16_t> wp((size_t)9 * cout * 64);
     for (int t = 0; t < 9; ++t)
         for (int o = 0; o < cout; ++o)
-            for (int c = 0; c < 32; ++c) {
-                const float x = 0.08f * rnd();
-                const uint16_t hi = f2bf(x);
-                uint32_t hu = (uint32_t)hi << 16;
-                float hf;
-                memcpy(&hf, &hu, 4);
-                const uint16_t lo = f2bf(x - hf);
-                const int uh = c / 8, ul = 4 + c / 8;
-                uint16_t* row = &wp[((size_t)t * cout + o) * 64];
-                row[(((uh + o) & 7) * 8) + c % 8] = hi;
-                row[(((ul + o) & 7) * 8) + c % 8] = lo;
-            }
+            for (int c = 0; c < 32; ++c) put_split(&wp[((size_t)t * cout + o) * 64], o, c, 0.08f * rnd());
     float *d_lm, *d_w1, *d_b1, *d_b2, *d_o1, *d_o2;
     bf16* d_w;
     const size_t out_n = (size_t)n * Hout * Wout * cout;

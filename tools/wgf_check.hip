@@ -74,7 +74,7 @@ int main(int argc, char** argv) {
                     double& m = ref[(((size_t)b * Ho + r / 3) * Wo + c / 3) * 32 + o];
                     m = std::max(m, s);
                 }
-    // conv_wg weight packing (aa_cnn.hip): step kh * 8 + e, [32 rows][8 units]
+    // conv_wg weight packing (pack_wg, aa_cnn_pack.h): step kh * 8 + e, [32 rows][8 units]
     std::vector<uint16_t> hw((size_t)3 * 8 * 32 * 64 * 2 + 1024, 0);
     for (int kh = 0; kh < 3; ++kh)
         for (int o = 0; o < 32; ++o)
@@ -83,12 +83,7 @@ int main(int argc, char** argv) {
                 for (int kw = 0; kw < 3; ++kw) w3[kw] = k2[((kh * 3 + kw) * 32 + c) * 32 + o];
                 for (int e = 0; e < 8; ++e) {
                     const double v = wg_g(6, e, 0) * w3[0] + wg_g(6, e, 1) * w3[1] + wg_g(6, e, 2) * w3[2];
-                    const size_t row = ((size_t)(kh * 8 + e) * 32 + o) * 64;
-                    const float wf = (float)v;
-                    const uint16_t hi = f2bf(wf);
-                    const int u = c / 8;
-                    hw[row + ((u + o) & 7) * 8 + c % 8] = hi;
-                    hw[row + ((u + 4 + o) & 7) * 8 + c % 8] = f2bf(wf - bf2f(hi));
+                    put_split(&hw[((size_t)(kh * 8 + e) * 32 + o) * 64], o, c, (float)v);
                 }
             }
     float *dx, *dw1, *db1, *db2, *dout;
