@@ -16,7 +16,7 @@ import torch  # noqa: F401  (must precede loading libaa.so, see above)
 
 # AA_LIB: an alternative build of the same library (tools/ab_build.py variants)
 LIB_PATH = Path(os.environ.get("AA_LIB") or Path(__file__).resolve().parent / "libaa.so")
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 AA_PREC_F32 = 0
 AA_PREC_BF16 = 1
@@ -85,6 +85,28 @@ class Node(C.Structure):
 AA_G = {"conv": 1, "dwconv": 2, "maxpool": 3, "avgpool": 4, "gmaxpool": 5, "gavgpool": 6, "add": 7, "mul": 8,
         "affine": 9, "dense": 10, "pow": 11}
 AA_GACT = {None: 0, "linear": 0, "relu": 1, "leaky": 2, "sigmoid": 3, "swish": 4}
+
+# aa_gkernel (include/aa.h): the launch a graph node was planned for
+AA_GK = {"x3p": 1, "x3t_256x16": 2, "x3t_128x32": 3, "x3t_64x128": 4, "x3t_split_kc2": 5, "x3t_split_kc1": 6,
+         "x3t_64x64_kc2": 7, "x3t_64x64_pd2": 8, "x3t_64x64": 9, "matvec": 10, "matvec_t": 11, "f32_s": 12,
+         "f32_lds_3x3x3": 13, "f32_lds_3x3x1": 14, "f32_lds": 15, "f32": 16, "dwpool4_s1": 17, "dwpool4_s2": 18,
+         "dwpool4_k3": 19, "dwpool4": 20, "dwpool": 21, "dw4": 22, "dw1": 23, "pool2d": 24, "gpool4": 25,
+         "gpool": 26, "binary": 27, "affine": 28, "pow": 29, "dense": 30}
+
+
+class NodePlan(C.Structure):
+    _fields_ = [
+        ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32), ("kernel", C.c_int32), ("bn", C.c_int32),
+        ("cout_pad", C.c_int32), ("cin_pad", C.c_int32), ("split", C.c_int32), ("cslice", C.c_int32),
+        ("skip", C.c_int32), ("nolaunch", C.c_int32), ("scale_src", C.c_int32), ("res_src", C.c_int32),
+        ("pool_into", C.c_int32), ("in0", C.c_int32), ("in1", C.c_int32), ("act", C.c_int32),
+        ("alpha", C.c_float), ("last_use", C.c_int32), ("off", C.c_int64),
+    ]
+
+
+class GraphLayout(C.Structure):
+    _fields_ = [("per_win", C.c_int64), ("part_off", C.c_int64), ("n_outputs", C.c_int32),
+                ("sigmoid_out", C.c_int32)]
 
 
 class SnConfig(C.Structure):
@@ -159,6 +181,12 @@ _SIGS = {
     "aa_graph_stage_time": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "aa_graph_stage_info": (C.c_int, [C.c_void_p, C.c_int32, C.c_char_p, C.c_int32, C.POINTER(C.c_double),
                                       C.POINTER(C.c_double)]),
+    "aa_graph_plan": (C.c_int, [C.POINTER(Node), C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
+                                C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "aa_graph_node_plan": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(NodePlan)]),
+    "aa_graph_plan_layout": (C.c_int, [C.c_void_p, C.POINTER(GraphLayout)]),
+    "aa_graph_node_image": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t,
+                                      C.POINTER(C.c_size_t)]),
     "aa_track_mean": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p,
                                 C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "aa_span_nonzero": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p,

@@ -203,4 +203,37 @@ static inline std::vector<uint16_t> gconv_pack_x3(const std::vector<float>& w_tc
     return h;
 }
 
+// The graph's images (aa_graph_plan.h) of a Keras kernel k = [K][cout], K =
+// tap * cin + c (HWIO flattened), no folding:
+// [tap][cout][cin], what gconv_pack_x3 takes
+static inline std::vector<float> keras_to_tco(const float* k, int ntap, int cin, int cout) {
+    std::vector<float> w((size_t)ntap * cout * cin);
+    for (int t = 0; t < ntap; ++t)
+        for (int o = 0; o < cout; ++o)
+            for (int c = 0; c < cin; ++c) w[((size_t)t * cout + o) * cin + c] = k[((size_t)t * cin + c) * cout + o];
+    return w;
+}
+
+// [cout][K]: gconv_f32 / gconv_f32_lds, gmatvec (1x1 convs on 1x1 maps, Dense)
+static inline std::vector<float> keras_to_ok(const float* k, int K, int cout) {
+    std::vector<float> w((size_t)cout * K);
+    for (int o = 0; o < cout; ++o)
+        for (int kk = 0; kk < K; ++kk) w[(size_t)o * K + kk] = k[(size_t)kk * cout + o];
+    return w;
+}
+
+// [K][cout], the Keras order as it is: gmatvec_t (one thread per output)
+static inline std::vector<float> keras_as_is(const float* k, int K, int cout) {
+    return std::vector<float>(k, k + (size_t)K * cout);
+}
+
+// [ceil(cout / 32)][K][32], channels past cout zero: gconv_f32_s (the f32
+// stem's weights through the scalar cache)
+static inline std::vector<float> pack_stem_f32(const float* k, int K, int cout) {
+    std::vector<float> w((size_t)((cout + 31) / 32) * K * 32, 0.f);
+    for (int o = 0; o < cout; ++o)
+        for (int kk = 0; kk < K; ++kk) w[((size_t)(o / 32) * K + kk) * 32 + o % 32] = k[(size_t)kk * cout + o];
+    return w;
+}
+
 }  // namespace aa

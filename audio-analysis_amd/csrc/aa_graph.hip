@@ -9,24 +9,33 @@
 // node by node over a batch of windows, each node's output an NHWC f32
 // tensor in a workspace region reused once its last consumer has run
 // (first-fit over the freed intervals).  Kernels:
-//   conv (C_in >= 16, split-bf16)  gconv_x3 (aa_gconv.h, MFMA)
-//   conv (C_in < 16, or f32 mode)  gconv_f32 (exact f32 FMA chains)
-//   depthwise conv                 gdwconv (one lane per output pixel and 4 channels)
-//   max / avg pool, global pools   gpool2d / ggpool
+//   conv (C_in >= 16, split-bf16)  gconv_x3t / gconv_x3p (aa_gconv.h, MFMA; split K: + gsplit_reduce)
+//   conv (C_in < 16, or f32 mode)  gconv_f32_s / gconv_f32_lds / gconv_f32 (exact f32 FMA chains)
+//   1x1 conv on a 1x1 map, dense   gmatvec / gmatvec_t
+//   depthwise conv                 gdwconv (one lane per output pixel and 4 channels);
+//                                  gdwconv_pool4 / gdwconv_pool with the global average pool that reads it
+//   max / avg pool, global pools   gpool2d / ggpool4 / ggpool
 //   add, broadcast multiply        gbinary
 //   affine / activation / pow      gaffine / gpow
-//   dense                          gdense
 // every one with its activation fused.
+//
+// This file: the kernels, upload_graph, graph_run_node (a switch over the
+// planned launch) and the entry points.  The plan itself -- shapes, weight
+// images, fusions, launch variants, workspace offsets -- is made on the host
+// by aa_graph_plan.h.
 #include <algorithm>
 #include <array>
 #include <cmath>
+#include <cstdarg>
+#include <cstdio>
 #include <cstring>
 #include <mutex>
 #include <string>
+#include <type_traits>
 
 #include "aa_common.h"
-#include "aa_cnn_pack.h"
 #include "aa_gconv.h"
+#include "aa_graph_plan.h"
 
 namespace aa {
 
@@ -416,64 +425,6 @@ __global__ __launch_bounds__(256) void gfinal(const float* __restrict__ x, float
     if (probs) probs[i] = sigmoid ? 1.f / (1.f + expf(-v)) : v;
 }
 
-struct GNode {
-    aa_node d;
-    int H = 0, W = 0, C = 0;  // output shape
-    int mfma = 0;             // conv on gconv_x3t
-    int bn = 64;              // its tile's output channels (16, 32, 64)
-    int split = 1, cslice = 0;  // pointwise conv on a small map: K split into `split` slices of cslice chunks
-    ConvGeom g{};
-    int cout_pad = 0;
-    void* d_w = nullptr;
-    float* d_b = nullptr;
-    float* d_b2 = nullptr;    // affine shift
-    float* d_ws = nullptr;    // f32 stem: weights [C_out / 32][K][32] for the scalar path (gconv_f32_s)
-    size_t off = 0;           // workspace offset (f32 elements per window)
-    // fusions (graph_build): a skipped node launches nothing; a conv may read
-    // a squeeze-and-excite scale [n][Cin] (the Multiply it replaces) and add a
-    // residual map (the Add it replaces) in its epilogue
-    bool skip = false;        // fused into a consumer: no launch, no buffer
-    bool nolaunch = false;    // written by its producer's launch (a pool fused into a dwconv)
-    int scale_src = -2, res_src = -2;
-    int pool_into = -2;       // dwconv: the global average pool node it also writes
-    int matvec = 0;           // 1x1 conv on a 1x1 map, or Dense: gmatvec on W[Cout][K]
-    int last_use = 0;
-    std::string name;
-    double flops = 0, bytes = 0;
-};
-
-struct Graph {
-    int prec = AA_PREC_BF16X3;
-    int in_h = 0, in_w = 0, in_c = 0;
-    std::vector<GNode> nodes;
-    size_t per_win = 0;  // workspace f32 elements per window
-    size_t part_off = 0; // split-K partial sums (per window, after the node buffers)
-    int L = 0;
-    int sigmoid_out = 0;
-    // HIP events around node launches (aa_graph_set_timing / aa_graph_time_stage):
-    // time_stage -1 every node, >= 0 that node only, -2 none
-    int time_stage = -2;
-    StageTimer timer;
-    // the forward's launches captured into HIP graphs, one per (input,
-    // batch, workspace, outputs, stream): a graph model issues one launch per
-    // node (~180 for an EfficientNetV2-B0), which from the host costs about
-    // as much as the kernels take on the device; a replay is one launch
-    struct Captured {
-        const float* x;
-        int n;
-        void* ws;
-        float* logits;
-        float* probs;
-        hipStream_t st;
-        hipGraphExec_t exec;
-        hipEvent_t done;  // recorded after every launch of exec: it may still run when evicted
-    };
-    std::vector<Captured> captured;
-    std::vector<Captured> seen;  // keys met once (captured the second time: a caller
-                                 // that allocates its outputs per call never pays a capture)
-    std::mutex cap_mu;
-};
-
 constexpr size_t AA_GRAPH_CAPTURES = 16;  // captured forwards kept per graph
 
 // an instantiated forward that may still be executing from its last launch:
@@ -492,578 +443,250 @@ static void free_graph(Graph* g) {
     if (!g) return;
     for (auto& c : g->captured) release_captured(c);
     g->timer.release();
-    for (auto& nd : g->nodes) {
-        (void)hipFree(nd.d_w);
-        (void)hipFree(nd.d_b);
-        (void)hipFree(nd.d_b2);
-        (void)hipFree(nd.d_ws);
-    }
+    if (g->uploaded)
+        for (auto& nd : g->nodes) {
+            (void)hipFree(nd.d_w);
+            (void)hipFree(nd.d_b);
+            (void)hipFree(nd.d_b2);
+            (void)hipFree(nd.d_ws);
+        }
     delete g;
 }
 
-static int gupload(void** dst, const void* src, size_t bytes) {
-    if (!bytes) return AA_OK;
-    AA_HIP(hipMalloc(dst, bytes));
-    AA_HIP(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
-    return AA_OK;
-}
-
-static const char* gop_name(int op) {
-    switch (op) {
-        case AA_G_CONV: return "conv";
-        case AA_G_DWCONV: return "dwconv";
-        case AA_G_MAXPOOL: return "maxpool";
-        case AA_G_AVGPOOL: return "avgpool";
-        case AA_G_GMAXPOOL: return "gmaxpool";
-        case AA_G_GAVGPOOL: return "gavgpool";
-        case AA_G_ADD: return "add";
-        case AA_G_MUL: return "mul";
-        case AA_G_AFFINE: return "affine";
-        case AA_G_DENSE: return "dense";
-        case AA_G_POW: return "pow";
-        default: return "?";
-    }
-}
-
-// Fusions on the built node list (bit-identical to the unfused graph: the
-// fused kernel computes the same f32 products and sums in the same order):
-// * Multiply(x [H][W][C], s [1][1][C]) whose only consumer is an MFMA conv:
-//   the conv scales its input channels while staging (squeeze-and-excite);
-// * Add(conv, r) where the conv has no activation and no other consumer and r
-//   is computed before the conv: the conv adds r in its epilogue and applies
-//   the add's activation (the residual of an inverted-bottleneck block).
-static void graph_fuse(Graph* G) {
-    const int n = (int)G->nodes.size();
-    std::vector<int> uses(n, 0);
-    for (const GNode& N : G->nodes)
-        for (int k : {N.d.in0, N.d.in1})
-            if (k >= 0) ++uses[k];
-    auto redirect = [&](int from, int to) {
-        for (GNode& N : G->nodes) {
-            if (N.d.in0 == from) N.d.in0 = to;
-            if (N.d.in1 == from) N.d.in1 = to;
-        }
+// Copies every node's host images to the device and releases them (an empty
+// image: the pointer stays null, which the kernels read as "absent").
+static int upload_graph(Graph* G) {
+    G->uploaded = true;  // from here on the nodes may own device memory
+    auto put = [](auto** d, auto& h) -> int {
+        const size_t bytes = h.size() * sizeof(h[0]);
+        if (!bytes) return AA_OK;
+        AA_HIP(hipMalloc((void**)d, bytes));
+        AA_HIP(hipMemcpy(*d, h.data(), bytes, hipMemcpyHostToDevice));
+        std::remove_reference_t<decltype(h)>().swap(h);
+        return AA_OK;
     };
-    for (int i = 0; i < n - 1; ++i) {
-        GNode& M = G->nodes[i];
-        if (M.d.op != AA_G_MUL || M.d.act != AA_GACT_NONE || uses[i] != 1 || M.d.in1 < 0) continue;
-        const GNode& S = G->nodes[M.d.in1];
-        if (!(S.H == 1 && S.W == 1 && (M.H != 1 || M.W != 1))) continue;
-        for (int j = i + 1; j < n; ++j) {
-            GNode& K = G->nodes[j];
-            if (K.d.in0 != i && K.d.in1 != i) continue;
-            if (K.d.op == AA_G_CONV && K.mfma && K.d.in0 == i && K.scale_src == -2) {
-                K.d.in0 = M.d.in0;
-                K.scale_src = M.d.in1;
-                M.skip = true;
-            }
-            break;
-        }
-    }
-    for (int i = 0; i < n - 1; ++i) {
-        GNode& A = G->nodes[i];
-        if (A.d.op != AA_G_ADD || A.d.in1 < 0) continue;
-        for (int side = 0; side < 2; ++side) {
-            const int x = side ? A.d.in1 : A.d.in0, r = side ? A.d.in0 : A.d.in1;
-            if (x < 0) continue;
-            GNode& X = G->nodes[x];
-            if (X.d.op != AA_G_CONV || !X.mfma || X.skip || X.d.act != AA_GACT_NONE || uses[x] != 1 ||
-                X.res_src != -2 || r >= x)
-                continue;
-            const bool same = r < 0 ? (G->in_h == X.H && G->in_w == X.W && G->in_c == X.C)
-                                    : (G->nodes[r].H == X.H && G->nodes[r].W == X.W && G->nodes[r].C == X.C);
-            if (!same || r < 0) continue;  // the graph input is not a workspace buffer
-            X.res_src = r;
-            X.d.act = A.d.act;
-            X.d.alpha = A.d.alpha;
-            X.bytes += 4.0 * X.H * X.W * X.C;
-            X.name += "+add";
-            A.skip = true;
-            redirect(i, x);
-            break;
-        }
-    }
-    for (int i = 0; i + 1 < n; ++i) {
-        GNode& D = G->nodes[i];
-        GNode& P = G->nodes[i + 1];
-        if (D.d.op == AA_G_DWCONV && P.d.op == AA_G_GAVGPOOL && P.d.in0 == i && i + 1 != n - 1) {
-            D.pool_into = i + 1;
-            P.nolaunch = true;
-            D.name += "+gap";
-        }
-    }
     for (GNode& N : G->nodes) {
-        if (N.scale_src >= 0) N.name += "+se";
-        if (N.nolaunch) {
-            N.name += "(fused)";
-            N.flops = N.bytes = 0;
-        }
-        if (N.skip) {
-            N.name += "(fused)";
-            N.flops = N.bytes = 0;
-        }
+        int rc = put(&N.d_w, N.h_w);
+        if (rc == AA_OK) rc = put(&N.d_ws, N.h_ws);
+        if (rc == AA_OK) rc = put(&N.d_b, N.h_b);
+        if (rc == AA_OK) rc = put(&N.d_b2, N.h_b2);
+        if (rc != AA_OK) return rc;
     }
-}
-
-// a pointwise conv over >= 384 channels on a small map (<= kSplitHW pixels
-// per window) is a short grid of long K loops: its K is split over blocks
-constexpr int kSplitHW = 128;
-
-static int graph_build(Graph* G, const aa_node* nodes, int n_nodes, const float* blob, int64_t blob_len) {
-    auto get = [&](int64_t off, int64_t n) -> const float* {
-        if (off < 0 || n < 0 || off + n > blob_len) return nullptr;
-        return blob + off;
-    };
-    G->nodes.resize(n_nodes);
-    for (int i = 0; i < n_nodes; ++i) {
-        GNode& N = G->nodes[i];
-        N.d = nodes[i];
-        const aa_node& d = N.d;
-        AA_CHECK(d.in0 >= -1 && d.in0 < i && d.in1 >= -1 && d.in1 < i, AA_ERR_INVALID,
-                 "aa_graph_create: node %d reads a later node", i);
-        AA_CHECK(d.act >= AA_GACT_NONE && d.act <= AA_GACT_SWISH, AA_ERR_INVALID, "node %d: activation %d", i, d.act);
-        auto shape = [&](int k, int& H, int& W, int& C) {
-            if (k < 0) { H = G->in_h; W = G->in_w; C = G->in_c; }
-            else { H = G->nodes[k].H; W = G->nodes[k].W; C = G->nodes[k].C; }
-        };
-        int H, W, C;
-        shape(d.in0, H, W, C);
-        const bool windowed = d.op == AA_G_CONV || d.op == AA_G_DWCONV || d.op == AA_G_MAXPOOL || d.op == AA_G_AVGPOOL;
-        if (windowed) {
-            AA_CHECK(d.kh >= 1 && d.kw >= 1 && d.sh >= 1 && d.sw >= 1 && d.pt >= 0 && d.pb >= 0 && d.pl >= 0 &&
-                         d.pr >= 0, AA_ERR_INVALID, "node %d: window / strides / pads", i);
-            N.H = (H + d.pt + d.pb - d.kh) / d.sh + 1;
-            N.W = (W + d.pl + d.pr - d.kw) / d.sw + 1;
-            AA_CHECK(H + d.pt + d.pb >= d.kh && W + d.pl + d.pr >= d.kw, AA_ERR_INVALID,
-                     "node %d: input %dx%d smaller than the window", i, H, W);
-        }
-        char nm[96];
-        switch (d.op) {
-            case AA_G_CONV: {
-                AA_CHECK(d.filters >= 1, AA_ERR_INVALID, "node %d: filters", i);
-                N.C = d.filters;
-                const int K = d.kh * d.kw * C;
-                const float* k = get(d.off[0], (int64_t)K * d.filters);
-                AA_CHECK(k, AA_ERR_INVALID, "node %d: conv kernel outside the blob", i);
-                const float* b = d.off[1] >= 0 ? get(d.off[1], d.filters) : nullptr;
-                AA_CHECK(d.off[1] < 0 || b, AA_ERR_INVALID, "node %d: bias outside the blob", i);
-                N.g = ConvGeom{H, W, C, N.H, N.W, N.C, d.kh, d.kw, d.sh, d.sw, d.pt, d.pl, (C + 31) / 32 * 32};
-                // a 1x1 conv on a 1x1 map is a matrix-vector product per window
-                // (squeeze-and-excite): exact f32 on gmatvec, not a 64-pixel MFMA tile
-                N.matvec = H == 1 && W == 1 && d.kh == 1 && d.kw == 1 && d.pt == 0 && d.pl == 0;
-                N.mfma = G->prec == AA_PREC_BF16X3 && C >= 16 && !N.matvec;
-                const int ntap = d.kh * d.kw;
-                int rc;
-                const bool pointwise = ntap == 1 && d.sh == 1 && d.sw == 1 && d.pt == 0 && d.pl == 0;
-                if (N.mfma) {
-                    N.bn = gconv_bn(N.C);
-                    N.cout_pad = (N.C + N.bn - 1) / N.bn * N.bn;
-                    std::vector<float> w_tco((size_t)ntap * N.C * C);
-                    for (int t = 0; t < ntap; ++t)
-                        for (int o = 0; o < N.C; ++o)
-                            for (int c = 0; c < C; ++c) w_tco[((size_t)t * N.C + o) * C + c] = k[((size_t)t * C + c) * N.C + o];
-                    const std::vector<uint16_t> h = gconv_pack_x3(w_tco, ntap, N.C, C, N.cout_pad, N.g.cin_pad);
-                    if ((rc = gupload(&N.d_w, h.data(), h.size() * 2)) != AA_OK) return rc;
-                    std::vector<float> bias(N.cout_pad, 0.f);
-                    for (int o = 0; o < N.C; ++o) bias[o] = b ? b[o] : 0.f;
-                    if ((rc = gupload((void**)&N.d_b, bias.data(), bias.size() * 4)) != AA_OK) return rc;
-                } else {
-                    // [Cout][K]; a matrix-vector product with K <= 64 keeps the
-                    // Keras [K][Cout] order (gmatvec_t: one thread per output)
-                    if (N.matvec && K <= 64) N.matvec = 2;
-                    std::vector<float> w_ohwc((size_t)N.C * K);
-                    for (int o = 0; o < N.C; ++o)
-                        for (int kk = 0; kk < K; ++kk) w_ohwc[(size_t)o * K + kk] = k[(size_t)kk * N.C + o];
-                    if ((rc = N.matvec == 2 ? gupload(&N.d_w, k, (size_t)K * N.C * 4)
-                                            : gupload(&N.d_w, w_ohwc.data(), w_ohwc.size() * 4)) != AA_OK)
-                        return rc;
-                    if (d.kh == 3 && d.kw == 3 && C == 3) {  // the scalar-path stem layout
-                        const int ng = (N.C + 31) / 32;
-                        std::vector<float> wsl((size_t)ng * K * 32, 0.f);
-                        for (int o = 0; o < N.C; ++o)
-                            for (int kk = 0; kk < K; ++kk)
-                                wsl[((size_t)(o / 32) * K + kk) * 32 + o % 32] = k[(size_t)kk * N.C + o];
-                        if ((rc = gupload((void**)&N.d_ws, wsl.data(), wsl.size() * 4)) != AA_OK) return rc;
-                    }
-                    std::vector<float> bias(N.C, 0.f);
-                    for (int o = 0; o < N.C; ++o) bias[o] = b ? b[o] : 0.f;
-                    if ((rc = gupload((void**)&N.d_b, bias.data(), bias.size() * 4)) != AA_OK) return rc;
-                }
-                N.flops = 2.0 * N.H * N.W * K * N.C;
-                N.bytes = 4.0 * (H * W * C + N.H * N.W * N.C);
-                // split K over blocks on small maps (shape-only choice: the
-                // sums do not depend on n)
-                if (N.mfma && pointwise && N.H * N.W <= kSplitHW) {
-                    const int ncc = N.g.cin_pad / 32;
-                    for (int cs : {6, 7, 4, 5, 8, 9})
-                        if (ncc >= 12 && ncc % cs == 0) {
-                            N.split = ncc / cs;
-                            N.cslice = cs;
-                            break;
-                        }
-                }
-                snprintf(nm, sizeof nm, "%s_%dx%d_s%d_%d_%d", N.mfma ? "conv_gx3" : N.matvec ? "matvec" : "conv_gf32",
-                         d.kh, d.kw, d.sh, C, N.C);
-                break;
-            }
-            case AA_G_DWCONV: {
-                N.C = C;
-                const float* k = get(d.off[0], (int64_t)d.kh * d.kw * C);
-                AA_CHECK(k, AA_ERR_INVALID, "node %d: depthwise kernel outside the blob", i);
-                const float* b = d.off[1] >= 0 ? get(d.off[1], C) : nullptr;
-                AA_CHECK(d.off[1] < 0 || b, AA_ERR_INVALID, "node %d: bias outside the blob", i);
-                int rc;
-                if ((rc = gupload(&N.d_w, k, (size_t)d.kh * d.kw * C * 4)) != AA_OK) return rc;
-                if (b && (rc = gupload((void**)&N.d_b, b, (size_t)C * 4)) != AA_OK) return rc;
-                N.flops = 2.0 * N.H * N.W * d.kh * d.kw * C;
-                N.bytes = 4.0 * (H * W * C + N.H * N.W * N.C);
-                snprintf(nm, sizeof nm, "dwconv_%dx%d_s%d_%d", d.kh, d.kw, d.sh, C);
-                break;
-            }
-            case AA_G_MAXPOOL:
-            case AA_G_AVGPOOL:
-                N.C = C;
-                N.bytes = 4.0 * (H * W * C + N.H * N.W * N.C);
-                snprintf(nm, sizeof nm, "%s_%dx%d_s%d_%d", gop_name(d.op), d.kh, d.kw, d.sh, C);
-                break;
-            case AA_G_GMAXPOOL:
-            case AA_G_GAVGPOOL:
-                N.H = N.W = 1;
-                N.C = C;
-                N.bytes = 4.0 * (H * W * C + C);
-                snprintf(nm, sizeof nm, "%s_%d", gop_name(d.op), C);
-                break;
-            case AA_G_ADD:
-            case AA_G_MUL: {
-                int H1, W1, C1;
-                shape(d.in1, H1, W1, C1);
-                const bool same = H1 == H && W1 == W && C1 == C;
-                const bool bc = d.op == AA_G_MUL && H1 == 1 && W1 == 1 && C1 == C;
-                AA_CHECK(same || bc, AA_ERR_UNSUPPORTED, "node %d: %s of %dx%dx%d and %dx%dx%d", i, gop_name(d.op), H,
-                         W, C, H1, W1, C1);
-                N.H = H; N.W = W; N.C = C;
-                N.bytes = 4.0 * (2 * H * W * C + H * W * C);
-                snprintf(nm, sizeof nm, "%s_%d", gop_name(d.op), C);
-                break;
-            }
-            case AA_G_AFFINE: {
-                N.H = H; N.W = W; N.C = C;
-                int rc;
-                if (d.off[0] >= 0) {
-                    const float* sc = get(d.off[0], C);
-                    AA_CHECK(sc, AA_ERR_INVALID, "node %d: scale outside the blob", i);
-                    if ((rc = gupload((void**)&N.d_b, sc, (size_t)C * 4)) != AA_OK) return rc;
-                }
-                if (d.off[1] >= 0) {
-                    const float* sh = get(d.off[1], C);
-                    AA_CHECK(sh, AA_ERR_INVALID, "node %d: shift outside the blob", i);
-                    if ((rc = gupload((void**)&N.d_b2, sh, (size_t)C * 4)) != AA_OK) return rc;
-                }
-                N.bytes = 8.0 * H * W * C;
-                snprintf(nm, sizeof nm, "affine_%d", C);
-                break;
-            }
-            case AA_G_POW:
-                N.H = H; N.W = W; N.C = C;
-                N.bytes = 8.0 * H * W * C;
-                snprintf(nm, sizeof nm, "pow_%d", C);
-                break;
-            case AA_G_DENSE: {
-                AA_CHECK(d.filters >= 1, AA_ERR_INVALID, "node %d: units", i);
-                const int K = H * W * C;
-                const float* k = get(d.off[0], (int64_t)K * d.filters);
-                AA_CHECK(k, AA_ERR_INVALID, "node %d: dense kernel outside the blob", i);
-                const float* b = d.off[1] >= 0 ? get(d.off[1], d.filters) : nullptr;
-                AA_CHECK(d.off[1] < 0 || b, AA_ERR_INVALID, "node %d: bias outside the blob", i);
-                int rc;
-                std::vector<float> w_ok((size_t)K * d.filters);  // [Cout][K] for gmatvec
-                for (int kk = 0; kk < K; ++kk)
-                    for (int o = 0; o < d.filters; ++o) w_ok[(size_t)o * K + kk] = k[(size_t)kk * d.filters + o];
-                if ((rc = gupload(&N.d_w, w_ok.data(), w_ok.size() * 4)) != AA_OK) return rc;
-                if (b && (rc = gupload((void**)&N.d_b, b, (size_t)d.filters * 4)) != AA_OK) return rc;
-                N.matvec = 1;
-                N.H = N.W = 1;
-                N.C = d.filters;
-                N.flops = 2.0 * K * d.filters;
-                N.bytes = 4.0 * (K + (double)K * d.filters + d.filters);
-                snprintf(nm, sizeof nm, "dense_%d_%d", K, d.filters);
-                break;
-            }
-            default:
-                AA_CHECK(false, AA_ERR_UNSUPPORTED, "node %d: op %d", i, d.op);
-        }
-        AA_CHECK(N.H >= 1 && N.W >= 1 && N.C >= 1, AA_ERR_INVALID, "node %d: empty output", i);
-        N.name = nm;
-    }
-    const int last = n_nodes - 1;
-    if (getenv("AA_GRAPH_NOFUSE") == nullptr) graph_fuse(G);
-    // liveness: a node's buffer is free after its last consumer; first fit
-    auto inputs = [&](const GNode& N) {
-        return std::array<int, 4>{N.d.in0, N.d.in1, N.scale_src, N.res_src};
-    };
-    for (int i = 0; i < n_nodes; ++i) G->nodes[i].last_use = i;
-    for (int i = 0; i < n_nodes; ++i) {
-        if (G->nodes[i].skip || G->nodes[i].nolaunch) continue;
-        for (int k : inputs(G->nodes[i]))
-            if (k >= 0) G->nodes[k].last_use = std::max(G->nodes[k].last_use, i);
-    }
-    G->nodes[last].last_use = n_nodes;  // the output survives the forward
-    std::vector<std::pair<size_t, size_t>> live;  // [begin, end) of buffers in use
-    size_t peak = 0;
-    std::vector<std::vector<int>> frees(n_nodes + 1);
-    // per-window sizes rounded up to 16 floats: every buffer starts 64-B
-    // aligned, so the float4 loads / stores of the kernels never straddle
-    auto node_sz = [&](int k) { return align_up((size_t)G->nodes[k].H * G->nodes[k].W * G->nodes[k].C, 16); };
-    auto alloc = [&](int k) {
-        const size_t sz = node_sz(k);
-        std::sort(live.begin(), live.end());
-        size_t at = 0;
-        for (auto& iv : live) {
-            if (iv.first >= at + sz) break;
-            at = std::max(at, iv.second);
-        }
-        G->nodes[k].off = at;
-        peak = std::max(peak, at + sz);
-        live.emplace_back(at, at + sz);
-        return at;
-    };
-    for (int i = 0; i < n_nodes; ++i) {
-        GNode& N = G->nodes[i];
-        if (N.skip || N.nolaunch) continue;  // (a nolaunch node is allocated with its producer)
-        const size_t sz = node_sz(i);
-        const size_t at = alloc(i);
-        if (N.pool_into >= 0) alloc(N.pool_into);
-        // release the inputs whose last use is this node
-        for (int k : inputs(N)) {
-            if (k < 0 || G->nodes[k].last_use != i) continue;
-            auto it = std::find(live.begin(), live.end(), std::make_pair(G->nodes[k].off, G->nodes[k].off + node_sz(k)));
-            if (it != live.end()) live.erase(it);
-        }
-        // a node nobody reads (a dangling branch) frees itself
-        if (N.last_use == i && i != last) {
-            auto it = std::find(live.begin(), live.end(), std::make_pair(at, at + sz));
-            if (it != live.end()) live.erase(it);
-        }
-    }
-    G->part_off = (peak + 63) / 64 * 64;
-    size_t part = 0;
-    for (const GNode& N : G->nodes)
-        if (N.split > 1 && !N.skip) part = std::max(part, (size_t)N.split * N.H * N.W * N.C);
-    G->per_win = G->part_off + (part + 63) / 64 * 64;
-    const GNode& O = G->nodes[last];
-    G->L = O.H * O.W * O.C;
-    G->sigmoid_out = O.d.act == AA_GACT_SIGMOID;
     return AA_OK;
 }
 
-// Tile and kernel choices of the graph's convs, fixed from in-pipeline A/B
-// runs (rounds 4-5; the rejected alternatives are no longer built):
-//  * 64 x 128 gconv_x3t tiles for short-K convs with C_out a multiple of 128,
-//    1x1 and larger kernels (42.3k -> 43.2k audio-s/s on the EfficientNetV2
-//    graph; 3x3 32->128 160 -> 147 us, profiles/r04/graph_ab_xcd.txt);
-//    128 x 64 tiles measured slower;
-//  * KC <= 2 chunks per K step (KC = 4 halves the blocks per CU);
-//  * two K steps in flight in the one-chunk 64 x 64 launches over >= 8 chunks
-//    (the 672 -> 112 project convs 46 -> 42 us; 3 steps and 64 / 128 x 224 /
-//    192 / 112 pointwise tiles slower, profiles/r05/graph_ab_pw.txt);
-//  * the depthwise conv + pool at 8 channel quads per 256-thread block and one
-//    pixel's taps per load batch (dwconv stages 526 -> 363 us against round
-//    5's column walk; 2 / 3 pixels 390 / 436 us, profiles/r05/graph_ab_dw.txt);
-//  * XCD-aware block order (stage sum 3016 -> 2923 us, graph_ab_xcd.txt);
-//  * gconv_x3p (patch-staged) for kernels > 1x1 at C_out <= 16 on 256-pixel
-//    tiles (3x3/32->16 212 -> 149 us); 128-pixel tiles and the stride-1
-//    patch + weight-ring kernel at 64 channels measured slower.
-constexpr int kGxKcMax = 2;
+// What every launch of a node needs: its input a (of shape Hin x Win x Cin),
+// its output, and the activation (the output node's sigmoid is applied by
+// gfinal: logits before it).
+struct NodeRun {
+    const Graph& G;
+    const GNode& N;
+    const float* x;
+    float* ws;
+    int n;
+    hipStream_t st;
+    const float* a;
+    float* out;
+    int Hin, Win, Cin;
+    int act;
+    const float* buf(int k) const { return k < 0 ? x : ws + G.nodes[k].off * (size_t)n; }
+};
 
+// the split-bf16 MFMA convs: gconv_x3p and the gconv_x3t tile shapes
+static int run_conv_mfma(const NodeRun& r) {
+    const GNode& N = r.N;
+    const aa_node& d = N.d;
+    const int n = r.n, act = r.act;
+    ConvGeom g = N.g;
+    int nz = n, scale_hw = 0;
+    if (is_pointwise(d)) {
+        // pointwise: the n windows' pixels are one [1][n H W] image
+        // (NHWC is [n][H][W][C] either way), so small maps fill whole
+        // tiles; a squeeze-and-excite scale is looked up per pixel's window
+        g.Hin = g.Hout = 1;
+        g.Win = g.Wout = N.H * N.W * n;
+        nz = 1;
+        scale_hw = N.H * N.W;
+    }
+    constexpr int xo = 1;  // XCD-aware block order (aa_gconv.h xcd_order)
+    const float* scl = N.scale_src >= 0 ? r.buf(N.scale_src) : nullptr;
+    const float* res = N.res_src >= 0 ? r.buf(N.res_src) : nullptr;
+    const int HWo = g.Hout * g.Wout;
+    auto x3t = [&](auto kern, dim3 grid, int cslice, float* part) {
+        hipLaunchKernelGGL(kern, grid, dim3(256), 0, r.st, r.a, (const uint16_t*)N.d_w, N.d_b, r.out, g, N.cout_pad,
+                           act, d.alpha, scl, res, scale_hw, cslice, part, xo);
+    };
+    const dim3 g64((HWo + 63) / 64, N.cout_pad / 64, nz);
+    switch (N.kernel) {
+        case AA_GK_X3P: {
+            constexpr int TH = kPatchTH, TW = kPatchTW;
+            const int tiles_w = (N.W + TW - 1) / TW, tiles_h = (N.H + TH - 1) / TH;
+            const size_t lds = (size_t)((TH - 1) * d.sh + d.kh) * ((TW - 1) * d.sw + d.kw) * GX_ROW * 4;
+            const dim3 grid((unsigned)(tiles_w * tiles_h), N.cout_pad / N.bn, n);
+            hipLaunchKernelGGL((gconv_x3p<4, 1, 4, 1, 16>), grid, dim3(256), lds, r.st, r.a, (const uint16_t*)N.d_w,
+                               N.d_b, r.out, g, N.cout_pad, act, d.alpha, TW, tiles_w, scl, res, xo);
+            break;
+        }
+        case AA_GK_X3T_256x16:
+            x3t(gconv_x3t<4, 1, 4, 1, 1, 1>, dim3((HWo + 255) / 256, N.cout_pad / 16, nz), 0, nullptr);
+            break;
+        case AA_GK_X3T_128x32:
+            x3t(gconv_x3t<4, 1, 2, 2, 1, 1>, dim3((HWo + 127) / 128, N.cout_pad / 32, nz), 0, nullptr);
+            break;
+        case AA_GK_X3T_64x128:
+            x3t(gconv_x3t<2, 2, 2, 4, 1, 1>, dim3((HWo + 63) / 64, N.cout_pad / 128, nz), 0, nullptr);
+            break;
+        case AA_GK_X3T_SPLIT_KC2:
+        case AA_GK_X3T_SPLIT_KC1: {
+            float* part = r.ws + r.G.part_off * (size_t)n;
+            const dim3 grid((HWo + 63) / 64, N.cout_pad / 64, N.split);
+            if (N.kernel == AA_GK_X3T_SPLIT_KC2) x3t(gconv_x3t<2, 2, 2, 2, 2, 1>, grid, N.cslice, part);
+            else x3t(gconv_x3t<2, 2, 2, 2, 1, 1>, grid, N.cslice, part);
+            AA_LAUNCH_CHECK();
+            const size_t total = (size_t)HWo * N.C;
+            hipLaunchKernelGGL(gsplit_reduce, dim3((unsigned)((total / 4 + 255) / 256 + 1)), dim3(256), 0, r.st, part,
+                               N.split, total, N.C, N.d_b, res, r.out, act, d.alpha);
+            break;
+        }
+        case AA_GK_X3T_64x64_KC2: x3t(gconv_x3t<2, 2, 2, 2, 2, 1>, g64, 0, nullptr); break;
+        case AA_GK_X3T_64x64_PD2: x3t(gconv_x3t<2, 2, 2, 2, 1, 2>, g64, 0, nullptr); break;
+        case AA_GK_X3T_64x64: x3t(gconv_x3t<2, 2, 2, 2, 1, 1>, g64, 0, nullptr); break;
+        default: return AA_ERR_UNSUPPORTED;
+    }
+    return AA_OK;
+}
+
+// exact f32: matrix-vector products and the gconv_f32 family
+static int run_conv_f32(const NodeRun& r) {
+    const GNode& N = r.N;
+    const aa_node& d = N.d;
+    const int n = r.n;
+    auto matvec = [&](auto kern, dim3 grid) {
+        hipLaunchKernelGGL(kern, grid, dim3(256), 0, r.st, r.a, (const float*)N.d_w, N.d_b, r.out, r.Cin, N.C, r.act,
+                           d.alpha);
+    };
+    auto conv = [&](auto kern, const float* w, int cpb) {  // cpb: output channels per block
+        hipLaunchKernelGGL(kern, dim3((N.H * N.W + 255) / 256, (N.C + cpb - 1) / cpb, n), dim3(256), 0, r.st, r.a, w,
+                           N.d_b, r.out, N.g, r.act, d.alpha);
+    };
+    switch (N.kernel) {
+        case AA_GK_MATVEC_T: matvec(gmatvec_t, dim3((N.C + 255) / 256, n)); break;
+        case AA_GK_MATVEC: matvec(gmatvec, dim3((N.C + 3) / 4, n)); break;
+        case AA_GK_F32_S: conv(gconv_f32_s<3, 3, 3>, N.d_ws, 32); break;
+        case AA_GK_F32_LDS_3x3x3: conv(gconv_f32_lds<3, 3, 3>, (const float*)N.d_w, 32); break;
+        case AA_GK_F32_LDS_3x3x1: conv(gconv_f32_lds<3, 3, 1>, (const float*)N.d_w, 32); break;
+        case AA_GK_F32_LDS: conv(gconv_f32_lds<>, (const float*)N.d_w, 32); break;
+        case AA_GK_F32: conv(gconv_f32, (const float*)N.d_w, 8); break;
+        default: return AA_ERR_UNSUPPORTED;
+    }
+    return AA_OK;
+}
+
+static int run_dwconv(const NodeRun& r) {
+    const GNode& N = r.N;
+    const aa_node& d = N.d;
+    const int n = r.n, Cin = r.Cin;
+    const size_t per = (size_t)N.H * N.W * N.C;
+    auto plain = [&](auto kern, int v) {
+        hipLaunchKernelGGL(kern, dim3((unsigned)((per / v + 255) / 256), n), dim3(256), 0, r.st, r.a,
+                           (const float*)N.d_w, N.d_b, r.out, r.Hin, r.Win, Cin, N.H, N.W, d.kh, d.kw, d.sh, d.sw, d.pt,
+                           d.pl, r.act, d.alpha);
+    };
+    // + the global average pool node it also writes; cpb: channels per block
+    auto pooled = [&](auto kern, int cpb, int threads) {
+        const GNode& P = r.G.nodes[N.pool_into];
+        hipLaunchKernelGGL(kern, dim3((Cin + cpb - 1) / cpb, n), dim3(threads), 0, r.st, r.a, (const float*)N.d_w,
+                           N.d_b, r.out, r.ws + P.off * (size_t)n, r.Hin, r.Win, Cin, N.H, N.W, d.kh, d.kw, d.sh, d.sw,
+                           d.pt, d.pl, r.act, d.alpha, P.d.act, P.d.alpha);
+    };
+    constexpr int Q = 8;  // channel quads per gdwconv_pool4 block
+    switch (N.kernel) {
+        case AA_GK_DWPOOL4_S1: pooled(gdwconv_pool4<Q, 3, 1, 1>, 4 * Q, Q * GP4_STRIPES); break;
+        case AA_GK_DWPOOL4_S2: pooled(gdwconv_pool4<Q, 3, 2, 1>, 4 * Q, Q * GP4_STRIPES); break;
+        case AA_GK_DWPOOL4_K3: pooled(gdwconv_pool4<Q, 3, 0, 1>, 4 * Q, Q * GP4_STRIPES); break;
+        case AA_GK_DWPOOL4: pooled(gdwconv_pool4<Q, 0, 0, 1>, 4 * Q, Q * GP4_STRIPES); break;
+        case AA_GK_DWPOOL: pooled(gdwconv_pool, 64, 64 * GP_STRIPES); break;
+        case AA_GK_DW4: plain(gdwconv<4>, 4); break;
+        case AA_GK_DW1: plain(gdwconv<1>, 1); break;
+        default: return AA_ERR_UNSUPPORTED;
+    }
+    return AA_OK;
+}
+
+// The launch planned for node N (aa_graph_plan.h choose_kernel): grids and
+// arguments only.
 static int graph_run_node(const Graph& G, const GNode& N, const float* x, float* ws, int n, hipStream_t st) {
     const aa_node& d = N.d;
-    auto buf = [&](int k) -> const float* {
-        return k < 0 ? x : ws + G.nodes[k].off * (size_t)n;
-    };
-    float* out = ws + N.off * (size_t)n;
-    const float* a = buf(d.in0);
-    int Hin, Win, Cin;
-    if (d.in0 < 0) { Hin = G.in_h; Win = G.in_w; Cin = G.in_c; }
-    else { Hin = G.nodes[d.in0].H; Win = G.nodes[d.in0].W; Cin = G.nodes[d.in0].C; }
-    // the output node's sigmoid is applied by gfinal (logits before it)
+    const GShape in = out_shape(G, d.in0);
     const bool last = &N == &G.nodes.back();
-    const int act = last && G.sigmoid_out ? AA_GACT_NONE : d.act;
+    NodeRun r{G, N, x, ws, n, st, nullptr, ws + N.off * (size_t)n, in.H, in.W, in.C,
+              last && G.sigmoid_out ? AA_GACT_NONE : d.act};
+    r.a = r.buf(d.in0);
+    const float* a = r.a;
+    float* out = r.out;
+    const int Hin = in.H, Win = in.W, Cin = in.C, act = r.act;
     const size_t per = (size_t)N.H * N.W * N.C;
-    switch (d.op) {
-        case AA_G_CONV:
-            if (N.mfma) {
-                ConvGeom g = N.g;
-                int nz = n, scale_hw = 0;
-                if (d.kh == 1 && d.kw == 1 && d.sh == 1 && d.sw == 1 && d.pt == 0 && d.pl == 0) {
-                    // pointwise: the n windows' pixels are one [1][n H W] image
-                    // (NHWC is [n][H][W][C] either way), so small maps fill whole
-                    // tiles; a squeeze-and-excite scale is looked up per pixel's window
-                    g.Hin = g.Hout = 1;
-                    g.Win = g.Wout = N.H * N.W * n;
-                    nz = 1;
-                    scale_hw = N.H * N.W;
-                }
-                constexpr int xo = 1;  // XCD-aware block order (aa_gconv.h xcd_order)
-                const float* scl = N.scale_src >= 0 ? buf(N.scale_src) : nullptr;
-                const float* res = N.res_src >= 0 ? buf(N.res_src) : nullptr;
-                const int HWo = g.Hout * g.Wout;
-                // kernels larger than 1x1 with C_out <= 16: the patch-staged
-                // kernel when its patch fits 64 KiB (two blocks per CU at least).
-                // (Measured on the EfficientNetV2 graph: 3x3/32->16 212 -> 149
-                // us; at 64 channels per block it lost -- 3x3/32->128 161 ->
-                // 178, 3x3/2 16->64 97 -> 176 us -- its per-tap B loads from L2
-                // stall the short tap loop: gconv_x3t keeps those.)
-                int BM = 0, TW = 0;
-                if (d.kh * d.kw > 1 && N.bn == 16) {
-                    BM = 256;
-                    TW = 16;
-                    const int TH = BM / TW;
-                    // every patch pixel staged (GX_P_STG items per thread) and the
-                    // patch within 64 KiB; otherwise gconv_x3t
-                    if (!gconv_x3p_fits((TH - 1) * d.sh + d.kh, (TW - 1) * d.sw + d.kw)) BM = 0;
-                }
-                if (BM) {
-                    const int TH = BM / TW;
-                    const int tiles_w = (N.W + TW - 1) / TW, tiles_h = (N.H + TH - 1) / TH;
-                    const size_t lds = (size_t)((TH - 1) * d.sh + d.kh) * ((TW - 1) * d.sw + d.kw) * GX_ROW * 4;
-                    const dim3 grid((unsigned)(tiles_w * tiles_h), N.cout_pad / N.bn, n);
-                    if (N.bn == 16)
-                        hipLaunchKernelGGL((gconv_x3p<4, 1, 4, 1, 16>), grid, dim3(256), lds, st, a,
-                                           (const uint16_t*)N.d_w, N.d_b, out, g, N.cout_pad, act, d.alpha, TW, tiles_w,
-                                           scl, res, xo);
-                    else if (N.bn == 32)
-                        hipLaunchKernelGGL((gconv_x3p<4, 1, 2, 2>), grid, dim3(256), lds, st, a, (const uint16_t*)N.d_w,
-                                           N.d_b, out, g, N.cout_pad, act, d.alpha, TW, tiles_w, scl, res, xo);
-                    else
-                        hipLaunchKernelGGL((gconv_x3p<2, 2, 2, 2>), grid, dim3(256), lds, st, a, (const uint16_t*)N.d_w,
-                                           N.d_b, out, g, N.cout_pad, act, d.alpha, TW, tiles_w, scl, res, xo);
-                } else {
-                    // gconv_x3t (64 x 64 by default)
-#define AA_X3T(GRID, WM_, WN_, MF_, NF_, KC_, PD_, CS_, PART_)                                                     \
-    hipLaunchKernelGGL((gconv_x3t<WM_, WN_, MF_, NF_, KC_, PD_>), GRID, dim3(256), 0, st, a, (const uint16_t*)N.d_w, \
-                       N.d_b, out, g, N.cout_pad, act, d.alpha, scl, res, scale_hw, CS_, PART_, xo)
-                    if (N.bn == 16)
-                        AA_X3T(dim3((HWo + 255) / 256, N.cout_pad / 16, nz), 4, 1, 4, 1, 1, 1, 0, nullptr);
-                    else if (N.bn == 32)
-                        AA_X3T(dim3((HWo + 127) / 128, N.cout_pad / 32, nz), 4, 1, 2, 2, 1, 1, 0, nullptr);
-                    else if (N.C >= 128 && N.g.cin_pad <= 256 && N.cout_pad % 128 == 0)
-                        // 64 x 128 tiles: half the re-reads of the pixel tile
-                        AA_X3T(dim3((HWo + 63) / 64, N.cout_pad / 128, nz), 2, 2, 2, 4, 1, 1, 0, nullptr);
-                    else if (N.split > 1 && nz == 1) {
-                        // split K: slices of cslice chunks on blockIdx.z, then the ordered sum
-                        float* part = ws + G.part_off * (size_t)n;
-                        const dim3 grid((HWo + 63) / 64, N.cout_pad / 64, N.split);
-                        if (N.cslice % 2 == 0) AA_X3T(grid, 2, 2, 2, 2, 2, 1, N.cslice, part);
-                        else AA_X3T(grid, 2, 2, 2, 2, 1, 1, N.cslice, part);
-                        AA_LAUNCH_CHECK();
-                        const size_t total = (size_t)HWo * N.C;
-                        hipLaunchKernelGGL(gsplit_reduce, dim3((unsigned)((total / 4 + 255) / 256 + 1)), dim3(256), 0, st,
-                                           part, N.split, total, N.C, N.d_b, res, out, act, d.alpha);
-                    } else {
-                        // 64 x 64 tiles, KC 32-channel chunks per K step (the same
-                        // products summed in the same order whatever KC is)
-                        const int ncc = N.g.cin_pad / 32;
-                        const int KC = ncc % 2 == 0 && kGxKcMax >= 2 ? 2 : 1;
-                        const dim3 grid((HWo + 63) / 64, N.cout_pad / 64, nz);
-                        if (KC == 2) AA_X3T(grid, 2, 2, 2, 2, 2, 1, 0, nullptr);
-                        else if (ncc >= 8) AA_X3T(grid, 2, 2, 2, 2, 1, 2, 0, nullptr);
-                        else AA_X3T(grid, 2, 2, 2, 2, 1, 1, 0, nullptr);
-                    }
-#undef AA_X3T
-                }
-            } else if (N.matvec == 2) {
-                hipLaunchKernelGGL(gmatvec_t, dim3((N.C + 255) / 256, n), dim3(256), 0, st, a, (const float*)N.d_w,
-                                   N.d_b, out, Cin, N.C, act, d.alpha);
-            } else if (N.matvec) {
-                hipLaunchKernelGGL(gmatvec, dim3((N.C + 3) / 4, n), dim3(256), 0, st, a, (const float*)N.d_w, N.d_b,
-                                   out, Cin, N.C, act, d.alpha);
-            } else if (d.kh * d.kw * Cin <= GF32_KMAX) {
-                const dim3 grid((N.H * N.W + 255) / 256, (N.C + 31) / 32, n);
-                if (N.d_ws)  // an RGB-style stem, weights through the scalar cache
-                    hipLaunchKernelGGL((gconv_f32_s<3, 3, 3>), grid, dim3(256), 0, st, a, (const float*)N.d_ws, N.d_b,
-                                       out, N.g, act, d.alpha);
-                else if (d.kh == 3 && d.kw == 3 && Cin == 3)
-                    hipLaunchKernelGGL((gconv_f32_lds<3, 3, 3>), grid, dim3(256), 0, st, a, (const float*)N.d_w, N.d_b,
-                                       out, N.g, act, d.alpha);
-                else if (d.kh == 3 && d.kw == 3 && Cin == 1)
-                    hipLaunchKernelGGL((gconv_f32_lds<3, 3, 1>), grid, dim3(256), 0, st, a, (const float*)N.d_w, N.d_b,
-                                       out, N.g, act, d.alpha);
-                else
-                    hipLaunchKernelGGL((gconv_f32_lds<>), grid, dim3(256), 0, st, a, (const float*)N.d_w, N.d_b, out,
-                                       N.g, act, d.alpha);
-            } else {
-                hipLaunchKernelGGL(gconv_f32, dim3((N.H * N.W + 255) / 256, (N.C + 7) / 8, n), dim3(256), 0, st, a,
-                                   (const float*)N.d_w, N.d_b, out, N.g, act, d.alpha);
-            }
-            break;
-        case AA_G_DWCONV:
-            if (N.pool_into >= 0) {
-                const GNode& P = G.nodes[N.pool_into];
-                float* pooled = ws + P.off * (size_t)n;
-                if ((Cin & 3) == 0) {
-#define AA_DWP(Q, KS, S, R)                                                                                    \
-    hipLaunchKernelGGL((gdwconv_pool4<Q, KS, S, R>), dim3((Cin + 4 * Q - 1) / (4 * Q), n), dim3(Q * GP4_STRIPES), 0, \
-                       st, a, (const float*)N.d_w, N.d_b, out, pooled, Hin, Win, Cin, N.H, N.W, d.kh, d.kw, d.sh,    \
-                       d.sw, d.pt, d.pl, act, d.alpha, P.d.act, P.d.alpha)
-                    const bool k3 = d.kh == 3 && d.kw == 3;
-                    const int cs = k3 && d.sh == d.sw && (d.sh == 1 || d.sh == 2) ? d.sh : 0;
-                    if (cs == 1) AA_DWP(8, 3, 1, 1);
-                    else if (cs == 2) AA_DWP(8, 3, 2, 1);
-                    else if (k3) AA_DWP(8, 3, 0, 1);
-                    else AA_DWP(8, 0, 0, 1);
-#undef AA_DWP
-                } else {
-                    hipLaunchKernelGGL(gdwconv_pool, dim3((Cin + 63) / 64, n), dim3(64 * GP_STRIPES), 0, st, a,
-                                       (const float*)N.d_w, N.d_b, out, pooled, Hin, Win, Cin, N.H, N.W, d.kh, d.kw,
-                                       d.sh, d.sw, d.pt, d.pl, act, d.alpha, P.d.act, P.d.alpha);
-                }
-            } else if ((Cin & 3) == 0)
-                hipLaunchKernelGGL(gdwconv<4>, dim3((unsigned)((per / 4 + 255) / 256), n), dim3(256), 0, st, a,
-                                   (const float*)N.d_w, N.d_b, out, Hin, Win, Cin, N.H, N.W, d.kh, d.kw, d.sh, d.sw,
-                                   d.pt, d.pl, act, d.alpha);
-            else
-                hipLaunchKernelGGL(gdwconv<1>, dim3((unsigned)((per + 255) / 256), n), dim3(256), 0, st, a,
-                                   (const float*)N.d_w, N.d_b, out, Hin, Win, Cin, N.H, N.W, d.kh, d.kw, d.sh, d.sw,
-                                   d.pt, d.pl, act, d.alpha);
-            break;
-        case AA_G_MAXPOOL:
-        case AA_G_AVGPOOL:
+    int rc = AA_OK;
+    switch (N.kernel) {
+        case AA_GK_X3P:
+        case AA_GK_X3T_256x16:
+        case AA_GK_X3T_128x32:
+        case AA_GK_X3T_64x128:
+        case AA_GK_X3T_SPLIT_KC2:
+        case AA_GK_X3T_SPLIT_KC1:
+        case AA_GK_X3T_64x64_KC2:
+        case AA_GK_X3T_64x64_PD2:
+        case AA_GK_X3T_64x64: rc = run_conv_mfma(r); break;
+        case AA_GK_MATVEC:
+        case AA_GK_MATVEC_T:
+        case AA_GK_F32_S:
+        case AA_GK_F32_LDS_3x3x3:
+        case AA_GK_F32_LDS_3x3x1:
+        case AA_GK_F32_LDS:
+        case AA_GK_F32: rc = run_conv_f32(r); break;
+        case AA_GK_DWPOOL4_S1:
+        case AA_GK_DWPOOL4_S2:
+        case AA_GK_DWPOOL4_K3:
+        case AA_GK_DWPOOL4:
+        case AA_GK_DWPOOL:
+        case AA_GK_DW4:
+        case AA_GK_DW1: rc = run_dwconv(r); break;
+        case AA_GK_POOL2D:
             hipLaunchKernelGGL(gpool2d, dim3((unsigned)((per + 255) / 256), n), dim3(256), 0, st, a, out, Hin, Win, Cin,
                                N.H, N.W, d.kh, d.kw, d.sh, d.sw, d.pt, d.pl, d.op == AA_G_AVGPOOL ? 1 : 0, act,
                                d.alpha);
             break;
-        case AA_G_GMAXPOOL:
-        case AA_G_GAVGPOOL:
-            if ((Cin & 3) == 0)
-                hipLaunchKernelGGL((ggpool4<16>), dim3((Cin + 63) / 64, n), dim3(16 * GP4_STRIPES), 0, st, a, out,
-                                   Hin, Win, Cin, d.op == AA_G_GAVGPOOL ? 1 : 0, act, d.alpha);
-            else
-                hipLaunchKernelGGL(ggpool, dim3((Cin + 63) / 64, n), dim3(64 * GP_STRIPES), 0, st, a, out, Hin * Win,
-                                   Cin, d.op == AA_G_GAVGPOOL ? 1 : 0, act, d.alpha);
+        case AA_GK_GPOOL4:
+            hipLaunchKernelGGL((ggpool4<16>), dim3((Cin + 63) / 64, n), dim3(16 * GP4_STRIPES), 0, st, a, out, Hin,
+                               Win, Cin, d.op == AA_G_GAVGPOOL ? 1 : 0, act, d.alpha);
             break;
-        case AA_G_ADD:
-        case AA_G_MUL: {
+        case AA_GK_GPOOL:
+            hipLaunchKernelGGL(ggpool, dim3((Cin + 63) / 64, n), dim3(64 * GP_STRIPES), 0, st, a, out, Hin * Win, Cin,
+                               d.op == AA_G_GAVGPOOL ? 1 : 0, act, d.alpha);
+            break;
+        case AA_GK_BINARY: {
             const GNode* B = d.in1 >= 0 ? &G.nodes[d.in1] : nullptr;
             const int bc = B ? (B->H == 1 && B->W == 1 && (N.H != 1 || N.W != 1)) : 0;
-            hipLaunchKernelGGL(gbinary, dim3((unsigned)((per + 255) / 256), n), dim3(256), 0, st, a, buf(d.in1), out,
+            hipLaunchKernelGGL(gbinary, dim3((unsigned)((per + 255) / 256), n), dim3(256), 0, st, a, r.buf(d.in1), out,
                                per, N.C, d.op == AA_G_MUL ? 1 : 0, bc, act, d.alpha);
             break;
         }
-        case AA_G_AFFINE:
+        case AA_GK_AFFINE:
             hipLaunchKernelGGL(gaffine, dim3((unsigned)((per * n + 255) / 256)), dim3(256), 0, st, a, N.d_b, N.d_b2,
                                out, per * n, N.C, act, d.alpha);
             break;
-        case AA_G_POW:
+        case AA_GK_POW:
             hipLaunchKernelGGL(gpow, dim3((unsigned)((per * n + 255) / 256)), dim3(256), 0, st, a, out, per * n,
                                d.alpha);
             break;
-        case AA_G_DENSE:
-            hipLaunchKernelGGL(gmatvec, dim3((N.C + 3) / 4, n), dim3(256), 0, st, a, (const float*)N.d_w, N.d_b,
-                               out, Hin * Win * Cin, N.C, act, d.alpha);
+        case AA_GK_DENSE:
+            hipLaunchKernelGGL(gmatvec, dim3((N.C + 3) / 4, n), dim3(256), 0, st, a, (const float*)N.d_w, N.d_b, out,
+                               Hin * Win * Cin, N.C, act, d.alpha);
             break;
         default:
             return AA_ERR_UNSUPPORTED;
     }
+    if (rc != AA_OK) return rc;
     AA_LAUNCH_CHECK();
     return AA_OK;
 }
@@ -1074,21 +697,57 @@ using namespace aa;
 
 extern "C" int aa_graph_create(const aa_node* nodes, int32_t n_nodes, const float* blob, int64_t blob_len,
                                int32_t in_h, int32_t in_w, int32_t in_c, int32_t precision, void** graph) {
-    AA_CHECK(nodes && blob && graph && n_nodes > 0, AA_ERR_INVALID, "aa_graph_create: null argument");
-    AA_CHECK(precision == AA_PREC_BF16X3 || precision == AA_PREC_F32, AA_ERR_UNSUPPORTED,
-             "aa_graph_create: graphs run in split-bf16 or f32 (precision %d)", precision);
-    AA_CHECK(in_h >= 1 && in_w >= 1 && in_c >= 1, AA_ERR_INVALID, "aa_graph_create: input shape");
-    Graph* G = new Graph();
-    G->prec = precision;
-    G->in_h = in_h;
-    G->in_w = in_w;
-    G->in_c = in_c;
-    const int rc = graph_build(G, nodes, n_nodes, blob, blob_len);
+    Graph* G = nullptr;
+    int rc = plan_graph(nodes, n_nodes, blob, blob_len, in_h, in_w, in_c, precision, graph ? &G : nullptr);
+    if (rc != AA_OK) return rc;
+    rc = upload_graph(G);
     if (rc != AA_OK) {
         free_graph(G);
         return rc;
     }
     *graph = G;
+    return AA_OK;
+}
+
+extern "C" int aa_graph_plan(const aa_node* nodes, int32_t n_nodes, const float* blob, int64_t blob_len, int32_t in_h,
+                             int32_t in_w, int32_t in_c, int32_t precision, void** graph) {
+    Graph* G = nullptr;
+    const int rc = plan_graph(nodes, n_nodes, blob, blob_len, in_h, in_w, in_c, precision, graph ? &G : nullptr);
+    if (rc == AA_OK) *graph = G;
+    return rc;
+}
+
+extern "C" int aa_graph_node_plan(const void* graph, int32_t node, aa_node_plan* out) {
+    const Graph* G = static_cast<const Graph*>(graph);
+    AA_CHECK(G && out && node >= 0 && node < (int)G->nodes.size(), AA_ERR_INVALID, "aa_graph_node_plan: bad argument");
+    const GNode& N = G->nodes[node];
+    *out = aa_node_plan{N.H, N.W, N.C, N.kernel, N.bn, N.cout_pad, N.g.cin_pad, N.split, N.cslice, N.skip, N.nolaunch,
+                        N.scale_src, N.res_src, N.pool_into, N.d.in0, N.d.in1, N.d.act, N.d.alpha, N.last_use,
+                        (int64_t)N.off};
+    return AA_OK;
+}
+
+extern "C" int aa_graph_plan_layout(const void* graph, aa_graph_layout* out) {
+    const Graph* G = static_cast<const Graph*>(graph);
+    AA_CHECK(G && out, AA_ERR_INVALID, "aa_graph_plan_layout: null argument");
+    *out = aa_graph_layout{(int64_t)G->per_win, (int64_t)G->part_off, G->L, G->sigmoid_out};
+    return AA_OK;
+}
+
+extern "C" int aa_graph_node_image(const void* graph, int32_t node, int32_t which, void* buf, size_t cap,
+                                   size_t* len) {
+    const Graph* G = static_cast<const Graph*>(graph);
+    AA_CHECK(G && len && node >= 0 && node < (int)G->nodes.size() && which >= 0 && which <= 3, AA_ERR_INVALID,
+             "aa_graph_node_image: bad argument");
+    AA_CHECK(!G->uploaded, AA_ERR_UNSUPPORTED,
+             "aa_graph_node_image: the host images are released once a graph is created; plan it (aa_graph_plan)");
+    const GNode& N = G->nodes[node];
+    const std::vector<float>& f = which == 1 ? N.h_b : which == 2 ? N.h_b2 : N.h_ws;
+    const void* src = which == 0 ? (const void*)N.h_w.data() : (const void*)f.data();
+    *len = which == 0 ? N.h_w.size() : f.size() * sizeof(float);
+    if (!buf) return AA_OK;  // a size query
+    AA_CHECK(cap >= *len, AA_ERR_INVALID, "aa_graph_node_image: buffer %zu < %zu", cap, *len);
+    if (*len) memcpy(buf, src, *len);
     return AA_OK;
 }
 
@@ -1136,6 +795,7 @@ extern "C" int aa_graph_forward(void* graph, const float* x, int32_t n, float* l
                                 size_t workspace_bytes, void* stream) {
     Graph* G = static_cast<Graph*>(graph);
     AA_CHECK(G && x && logits, AA_ERR_INVALID, "aa_graph_forward: null argument");
+    AA_CHECK(G->uploaded, AA_ERR_INVALID, "aa_graph_forward: the graph is a plan (aa_graph_plan), not created");
     if (n <= 0) return AA_OK;
     constexpr int32_t CHUNK = 32768;  // grids carry the window in blockIdx.y / z
     const int32_t nc0 = std::min(n, CHUNK);

@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define AA_ABI_VERSION 4
+#define AA_ABI_VERSION 5
 
 typedef enum aa_status {
     AA_OK = 0,
@@ -276,6 +276,78 @@ int aa_graph_time_stage(void* graph, int32_t stage);
 int aa_graph_stage_time(void* graph, int32_t stage, double* total_ms, int64_t* count);
 int aa_graph_stage_info(const void* graph, int32_t stage, char* name, int32_t name_len, double* flops_per_item,
                         double* bytes_per_item);
+
+/* The launch a node was planned for, chosen once from its shape when the
+ * graph is planned (csrc/aa_graph_plan.h choose_kernel). */
+typedef enum aa_gkernel {
+    AA_GK_X3P = 1,             /* gconv_x3p: patch-staged, 256 pixels x 16 channels */
+    AA_GK_X3T_256x16 = 2,      /* gconv_x3t tiles (pixels x channels) */
+    AA_GK_X3T_128x32 = 3,
+    AA_GK_X3T_64x128 = 4,
+    AA_GK_X3T_SPLIT_KC2 = 5,   /* split K (+ gsplit_reduce), 2 / 1 chunks per K step */
+    AA_GK_X3T_SPLIT_KC1 = 6,
+    AA_GK_X3T_64x64_KC2 = 7,
+    AA_GK_X3T_64x64_PD2 = 8,   /* one chunk per step, two steps in flight */
+    AA_GK_X3T_64x64 = 9,
+    AA_GK_MATVEC = 10,         /* gmatvec: 1x1 conv on a 1x1 map */
+    AA_GK_MATVEC_T = 11,       /* gmatvec_t: the same with K <= 64 */
+    AA_GK_F32_S = 12,          /* gconv_f32_s<3, 3, 3> */
+    AA_GK_F32_LDS_3x3x3 = 13,  /* gconv_f32_lds<3, 3, 3> */
+    AA_GK_F32_LDS_3x3x1 = 14,  /* gconv_f32_lds<3, 3, 1> */
+    AA_GK_F32_LDS = 15,        /* gconv_f32_lds<> */
+    AA_GK_F32 = 16,            /* gconv_f32 */
+    AA_GK_DWPOOL4_S1 = 17,     /* gdwconv_pool4<8, 3, 1, 1> */
+    AA_GK_DWPOOL4_S2 = 18,     /* gdwconv_pool4<8, 3, 2, 1> */
+    AA_GK_DWPOOL4_K3 = 19,     /* gdwconv_pool4<8, 3, 0, 1> */
+    AA_GK_DWPOOL4 = 20,        /* gdwconv_pool4<8, 0, 0, 1> */
+    AA_GK_DWPOOL = 21,         /* gdwconv_pool */
+    AA_GK_DW4 = 22,            /* gdwconv<4> */
+    AA_GK_DW1 = 23,            /* gdwconv<1> */
+    AA_GK_POOL2D = 24,         /* gpool2d */
+    AA_GK_GPOOL4 = 25,         /* ggpool4<16> */
+    AA_GK_GPOOL = 26,          /* ggpool */
+    AA_GK_BINARY = 27,         /* gbinary */
+    AA_GK_AFFINE = 28,         /* gaffine */
+    AA_GK_POW = 29,            /* gpow */
+    AA_GK_DENSE = 30,          /* gmatvec over the flattened map */
+} aa_gkernel;
+
+/* One node of a planned graph, after the fusion passes. */
+typedef struct aa_node_plan {
+    int32_t H, W, C;                     /* output shape */
+    int32_t kernel;                      /* aa_gkernel */
+    int32_t bn, cout_pad, cin_pad;       /* MFMA convs: channel tile, padded C_out, C_in */
+    int32_t split, cslice;               /* split K: slices, 32-channel chunks per slice */
+    int32_t skip, nolaunch;              /* fused into a consumer / written by its producer */
+    int32_t scale_src, res_src;          /* conv: squeeze-and-excite scale, residual (-2: none) */
+    int32_t pool_into;                   /* depthwise conv: the global average pool it also writes (-2) */
+    int32_t in0, in1, act;               /* aa_node's, as the fusions left them */
+    float alpha;
+    int32_t last_use;                    /* last node that reads the output */
+    int64_t off;                         /* workspace offset, f32 elements per window */
+} aa_node_plan;
+
+/* The workspace of a planned graph, per window in f32 elements: node buffers
+ * in [0, part_off), split-K partial sums in [part_off, per_win). */
+typedef struct aa_graph_layout {
+    int64_t per_win, part_off;
+    int32_t n_outputs, sigmoid_out;      /* the output node's sigmoid is applied after the logits */
+} aa_graph_layout;
+
+/* The plan alone, on the host (as aa_model_plan): aa_graph_create's
+ * arguments, checks, return codes and aa_last_error texts, but no device
+ * memory and no HIP call.  aa_graph_n_stages / stage_info / n_outputs /
+ * workspace_bytes / destroy serve a planned graph; aa_graph_forward returns
+ * AA_ERR_INVALID.
+ * node_image copies out the bytes aa_graph_create would upload for a node
+ * (the aa_model_stage_image contract): which = 0 the weights, 1 the bias (an
+ * affine node: its scale), 2 an affine node's shift, 3 the f32 stem's
+ * [C_out / 32][K][32] image; len 0: the node reads a null pointer. */
+int aa_graph_plan(const aa_node* nodes, int32_t n_nodes, const float* blob, int64_t blob_len, int32_t in_h,
+                  int32_t in_w, int32_t in_c, int32_t precision, void** graph);
+int aa_graph_node_plan(const void* graph, int32_t node, aa_node_plan* out);
+int aa_graph_plan_layout(const void* graph, aa_graph_layout* out);
+int aa_graph_node_image(const void* graph, int32_t node, int32_t which, void* buf, size_t cap, size_t* len);
 
 /* ---------------- ensemble + window mean ---------------- */
 /* probs: device float32, model m / window w at probs[m * model_stride + w * n_labels].

@@ -26,7 +26,7 @@ def test_library_exports_every_declared_symbol():
 
 
 def test_abi_version_and_struct_sizes():
-    assert _lib.lib().aa_abi_version() == _lib.ABI_VERSION == 4
+    assert _lib.lib().aa_abi_version() == _lib.ABI_VERSION == 5
     assert C.sizeof(_lib.Window) == 16
     assert C.sizeof(_lib.Layer) == 6 * 4 + 4 * 8
     assert C.sizeof(_lib.FeConfig) == 12 * 4
