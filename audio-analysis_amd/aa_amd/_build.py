@@ -13,7 +13,7 @@ CSRC = PKG.parent / "csrc"
 INCLUDE = PKG.parent.parent / "include"
 LIB = PKG / "libaa.so"
 SOURCES = ["aa_api.cpp", "aa_frontend.hip", "aa_cnn.hip", "aa_scan.hip", "aa_signal.hip", "aa_flac.cpp",
-           "aa_vorbis.cpp", "aa_tracks.cpp", "aa_resample.hip", "aa_graph.hip"]
+           "aa_vorbis.cpp", "aa_tracks.cpp", "aa_resample.hip", "aa_graph.hip", "aa_sosfilt.hip"]
 ARCH = os.environ.get("AA_OFFLOAD_ARCH", "gfx950")
 # per-source flags: the FFT front end is written in scalar f32; SLP packing it
 # into v_pk_* ops needs paired SGPR constants and register shuffles that push
@@ -31,7 +31,11 @@ EXTRA_FLAGS = {"aa_frontend.hip": ["-fno-slp-vectorize"], "aa_signal.hip": ["-fn
                # same for the graph route: the split-bf16 1x1 / expand convs are
                # VALU-issue-bound too (effnetv2 step 61.0k -> 62.5k audio-s/s,
                # profiles/r06/ab_graph_noslp.txt)
-               "aa_graph.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"]}
+               "aa_graph.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"],
+               # scipy's sosfilt arithmetic, operation by operation: the kernels
+               # name every rounding (__dmul_rn / __dadd_rn); this keeps the
+               # host's one-step matrix (aa_sosfilt_plan) uncontracted too
+               "aa_sosfilt.hip": ["-ffp-contract=off"]}
 
 
 def hipcc() -> str:

@@ -129,6 +129,20 @@ class VorbisInfo(C.Structure):
                 ("blocksize_1", C.c_int32), ("total_frames", C.c_int64)]
 
 
+# the band-pass filter's geometry (include/aa.h AA_SOS_*)
+AA_SOS_MAX_SECTIONS = 2
+AA_SOS_CHUNK = 32
+AA_SOS_BLOCK = 8192
+AA_SOS_LEVELS = 16
+AA_SOS_MAX_N = 1 << 28
+
+
+class SosJob(C.Structure):
+    _fields_ = [("src", C.c_int64), ("n", C.c_int64), ("dst", C.c_int64), ("n_sections", C.c_int32),
+                ("n_levels", C.c_int32), ("sos", C.c_double * 12), ("p", C.c_double * 16),
+                ("pw", C.c_double * 256)]
+
+
 _lib = None
 
 _SIGS = {
@@ -191,6 +205,10 @@ _SIGS = {
                                 C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "aa_span_nonzero": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p,
                                   C.c_void_p]),
+    "aa_sosfilt_plan": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.POINTER(SosJob)]),
+    "aa_sosfilt_workspace_bytes": (C.c_size_t, [C.POINTER(SosJob), C.c_int32]),
+    "aa_sosfilt_run": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_size_t,
+                                 C.c_void_p]),
     "aa_pcm_s16_to_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
     "aa_resample_poly": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                    C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),

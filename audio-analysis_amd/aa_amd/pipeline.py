@@ -26,6 +26,7 @@ import torch
 
 from .frontend import FeSettings, FrontEnd, pack_windows
 from .model import Model, track_mean
+from .sosfilt import filtered_sources_device, run as sosfilt_run, workspace_bytes as sosfilt_workspace_bytes
 from .windows import filtered_sources, schedule
 
 
@@ -54,15 +55,22 @@ class Classifier:
     _shared = {}
 
     @classmethod
-    def shared(cls, precision=None, device=None):
+    def shared(cls, precision=None, device=None, sosfilt=None):
         precision = precision or os.environ.get("AA_PRECISION", "bf16x3")
-        key = (precision, str(device or "cuda"))
+        sosfilt = sosfilt or os.environ.get("AA_SOSFILT") or "host"
+        key = (precision, str(device or "cuda"), sosfilt)
         if key not in cls._shared:
-            cls._shared[key] = cls(precision, device)
+            cls._shared[key] = cls(precision, device, sosfilt)
         return cls._shared[key]
 
-    def __init__(self, precision="bf16x3", device=None):
+    def __init__(self, precision="bf16x3", device=None, sosfilt=None):
+        """``sosfilt``: where the band-pass filter of filter_freq /
+        filter_below groups runs: "host" (scipy's sosfilt, the default; also
+        from AA_SOSFILT) or "gpu" (aa_sosfilt_run on the uploaded PCM)."""
         self.precision = precision
+        self.sosfilt = sosfilt or os.environ.get("AA_SOSFILT") or "host"
+        if self.sosfilt not in ("host", "gpu"):
+            raise ValueError(f"sosfilt must be 'host' or 'gpu', not {self.sosfilt!r}")
         self.device = torch.device(device or "cuda")
         self._models = {}
         self._fes = {}
@@ -132,8 +140,8 @@ class Classifier:
             if model_name == "embeddings":
                 raise NotImplementedError("tensorflow_hub embedding models need a network fetch")
             if views is None:
-                views, extras = [], []
-                extra_at = int(pcm.numel())
+                views, extras, sos_jobs = [], [], []
+                n_pcm = extra_at = int(pcm.numel())
                 for i, r in enumerate(recs):
                     try:
                         if r.seed is not None:
@@ -148,7 +156,14 @@ class Classifier:
                         # band-pass filtered tracks (:152-162): their windows read a
                         # filtered copy appended after the batch's samples
                         ff, fb = meta.get("filter_freq", False), meta.get("filter_below", None)
-                        if ff or fb:
+                        if (ff or fb) and self.sosfilt == "gpu":
+                            # the device filters pcm's own samples into the tail:
+                            # no host samples (r.frames), no second upload
+                            jobs, v = filtered_sources_device(pcm, n_pcm, r.off, sr, r.tracks, v, spans, ff, fb,
+                                                              extra_at - r.off)
+                            sos_jobs.extend(jobs)
+                            extra_at += sum(j.n for j in jobs)
+                        elif ff or fb:
                             extra, v = filtered_sources(r.frames(), sr, r.tracks, v, spans, ff, fb, extra_at - r.off)
                             if len(extra):
                                 extras.append(extra)
@@ -161,6 +176,11 @@ class Classifier:
                     views.append([[(src + r.off, n, p) for (src, n, p) in tv] for tv in v])
                 if extras:
                     pcm = torch.cat([pcm, torch.from_numpy(np.concatenate(extras)).to(dev)])
+                if sos_jobs:
+                    grown = torch.empty(extra_at, dtype=torch.float32, device=dev)  # the tail: the jobs' output
+                    grown[:n_pcm].copy_(pcm.reshape(-1))
+                    pcm = grown
+                    sosfilt_run(pcm, sos_jobs, workspace=_grow(ws, "sos", sosfilt_workspace_bytes(sos_jobs), dev))
                 flat = [w for rv in views for tv in rv for w in tv]
                 fe = self.frontend(s)
                 if flat:
@@ -242,7 +262,7 @@ class BatchRec:
     n: int                 # samples
     off: int               # first sample in the batch's device PCM
     tracks: list           # Signal objects; results are appended to them
-    frames: object         # callable -> host float32 samples (band-pass filtering only)
+    frames: object         # callable -> host float32 samples (band-pass filtering on the host only)
     seed: object = None    # np.random.seed before this recording's window schedule
 
 

@@ -20,6 +20,8 @@
  *                MagTransform.call                  src/magtransformv2.py:19-21
  *   aa_track_mean  np.mean over models, windows     src/identify_tracks.py:547-551
  *   aa_span_nonzero  get_end                        src/identify_tracks.py:387-413
+ *   aa_sosfilt_*  butter_bandpass_filter's sosfilt   src/identify_tracks.py:152-162,
+ *                                                      :1036-1056
  *   aa_pcm_s16_to_f32  load_recording's s16 -> f32  src/identify_tracks.py:49-62
  *   aa_resample_poly   load_recording's resample     src/identify_tracks.py:49-62
  *   aa_sn_*      signal_noise                       src/identify_tracks.py:650-706
@@ -365,6 +367,59 @@ int aa_track_mean(const float* probs, int32_t n_models, int64_t model_stride, in
  * a constant mel block exactly when every sample its frames cover is zero. */
 int aa_span_nonzero(const float* pcm, int64_t n, const int64_t* spans, int32_t n_spans,
                     int32_t* flags, void* stream);
+
+/* ---------------------------------------------------------------- band-pass filter */
+/* butter_bandpass_filter's sosfilt over a track's sample range
+ * (src/identify_tracks.py:152-162, :1036-1056): y = scipy.signal.sosfilt(sos,
+ * x) with zero initial state, for a batch of jobs in one device PCM buffer.
+ * f32 in, scipy's float64 direct-form-II-transposed arithmetic in scipy's
+ * order (no fused multiply-add), one rounding to f32 out.
+ *
+ * The recurrence is linear in its 4-vector state (z0, z1 of section 0, then
+ * of section 1): a zero-input step is s <- P s.  A job is cut into chunks of
+ * AA_SOS_CHUNK samples, one lane each, AA_SOS_BLOCK samples per workgroup:
+ * every lane runs its chunk from zero state, the end states are scanned with
+ * the powers of P (inside the workgroup, then over the workgroups' aggregates
+ * in a launch of its own), and every lane reruns its chunk from its true
+ * start state.  Three launches, no workgroup waits on another. */
+#define AA_SOS_MAX_SECTIONS 2
+#define AA_SOS_CHUNK 32          /* samples per lane */
+#define AA_SOS_BLOCK 8192        /* samples per workgroup: 256 lanes x AA_SOS_CHUNK */
+#define AA_SOS_LEVELS 16         /* powers kept: P^(AA_SOS_CHUNK 2^k), k < 16 */
+#define AA_SOS_MAX_N 268435456   /* samples per job, 2^28 */
+
+/* One filter job: pcm[src, src + n) -> pcm[dst, dst + n).  Made on the host
+ * by aa_sosfilt_plan, device-resident array for aa_sosfilt_run. */
+typedef struct aa_sos_job {
+    int64_t src, n, dst;         /* sample offsets into the PCM buffer */
+    int32_t n_sections;          /* 1 (low-pass) or 2 (band-pass) */
+    int32_t n_levels;            /* AA_SOS_LEVELS */
+    double sos[12];              /* scipy rows b0 b1 b2 a0 a1 a2 */
+    double p[16];                /* P, row-major: one zero-input step of the state */
+    double pw[256];              /* level k at pw + 16 k: P^(AA_SOS_CHUNK 2^k) */
+} aa_sos_job;
+
+/* Host only, no HIP call.  sos: n_sections (1 or 2) scipy rows with a0 == 1
+ * and finite coefficients; 0 <= n <= AA_SOS_MAX_N; src, dst >= 0.  P comes
+ * from stepping unit states with zero input in the kernel's arithmetic, its
+ * powers from repeated squaring in long double, rounded to double.
+ * AA_ERR_INVALID (reason in aa_last_error) otherwise, also for a filter whose
+ * powers overflow. */
+int aa_sosfilt_plan(const double* sos, int32_t n_sections, int64_t src, int64_t n, int64_t dst, aa_sos_job* job);
+/* Workspace of one aa_sosfilt_run over these (host) jobs; 0 for none. */
+size_t aa_sosfilt_workspace_bytes(const aa_sos_job* jobs_host, int32_t n_jobs);
+/* Runs every job (jobs_dev: device array; max_n: the largest job's n).
+ * No dst range may overlap a src range or another dst range.  Before any
+ * launch: null pointers and max_n > n_pcm or > AA_SOS_MAX_N are
+ * AA_ERR_INVALID, a short workspace AA_ERR_WORKSPACE; n_jobs == 0 is AA_OK.
+ * The jobs themselves are device memory the host cannot read: the kernels
+ * skip a job (nothing read or written) whose ranges leave [0, n_pcm) or whose
+ * n exceeds max_n, so callers validate ranges where they plan the jobs
+ * (aa_amd/sosfilt.py does).  Non-finite input behaves as in the sequential
+ * filter: output before it is unaffected, all output from it on is
+ * non-finite.  Allocates nothing; capturable. */
+int aa_sosfilt_run(float* pcm, int64_t n_pcm, const aa_sos_job* jobs_dev, int32_t n_jobs, int64_t max_n,
+                   void* workspace, size_t workspace_bytes, void* stream);
 
 /* Device PCM16 (interleaved, `channels` <= 8) -> mono f32, as load_recording
  * delivers it (src/identify_tracks.py:49-62: ffmpeg s16, librosa buf_to_float
