@@ -1191,9 +1191,9 @@ static int launch_x3(const Stage& s, const void* in, void* out, int n, hipStream
 }
 
 template <int KH, int CIN, int WM, int WN, int MF, int NF, int POOL, int TH, int TW, int OCC, int WO, int NPASS,
-          int BD, bool IN_SPLIT, bool OUT_SPLIT>
+          int BD, int SLIDE, bool IN_SPLIT, bool OUT_SPLIT>
 static int launch_wg(const Stage& s, const void* in, void* out, int n, hipStream_t st) {
-    auto k = conv_wg<KH, CIN, WM, WN, MF, NF, POOL, TH, TW, OCC, IN_SPLIT, OUT_SPLIT, 0, WO, NPASS, BD>;
+    auto k = conv_wg<KH, CIN, WM, WN, MF, NF, POOL, TH, TW, OCC, IN_SPLIT, OUT_SPLIT, 0, WO, NPASS, BD, SLIDE>;
     constexpr int BN = WN * NF * 16;
     const size_t lds = wg_lds_bytes<KH, BN, TH, TW, WO, NPASS, WN>();
     return launch_tuned(s, nullptr, n, (const void*)k, lds, true, POOL, TH, TW, BN,
@@ -1326,11 +1326,11 @@ static int launch_stage(const Model& m, const Stage& s, const void* in, void* ou
     }
     if constexpr (is_split<T>()) {
         if (s.wg) {
-#define AA_LAUNCHW(KH, CIN, POOL, WM, WN, MF, NF, TH, TW, OCC, WO, NPASS, BD)                                    \
+#define AA_LAUNCHW(KH, CIN, POOL, WM, WN, MF, NF, TH, TW, OCC, WO, NPASS, BD, SLIDE)                             \
             if (s.kh == KH && s.cin == CIN && s.pool == POOL)                                                    \
                 return dispatch_split<false>(s, [&](auto, auto is, auto os) {                                    \
-                    return launch_wg<KH, CIN, WM, WN, MF, NF, POOL, TH, TW, OCC, WO, NPASS, BD, decltype(is)::value, \
-                                     decltype(os)::value>(s, in, out, n, st);                                    \
+                    return launch_wg<KH, CIN, WM, WN, MF, NF, POOL, TH, TW, OCC, WO, NPASS, BD, SLIDE,           \
+                                     decltype(is)::value, decltype(os)::value>(s, in, out, n, st);               \
                 });
             AA_WG_CFGS(AA_LAUNCHW)
 #undef AA_LAUNCHW

@@ -51,7 +51,9 @@ namespace aa {
 // pool) of kernel-width-3 convs -> waves (WM x WN), fragments per wave (MF x
 // NF, each with WO + 2 accumulator sets), output tile TH x TW (TW a multiple
 // of WO), pinned waves per SIMD (0: free), outputs per group WO, staging
-// passes NPASS, B fragment sets in flight BD.  Preferred over conv_x3 where a row exists (the
+// passes NPASS, B fragment sets in flight BD, A fragments sliding in registers
+// (SLIDE, aa_conv_wg.h: 0 reads them from LDS at every kernel row, S every S
+// rows).  Preferred over conv_x3 where a row exists (the
 // fused first-layer stage always runs conv_x3).  In-pipeline A/B (tools/ab.sh,
 // same box): the 9x3 layer 187 -> 160 us, step 180k -> 193k audio-s/s; the
 // small 3x3 / 1x3 layers lose on it (their transform-heavy staging outweighs
@@ -62,8 +64,10 @@ namespace aa {
 // F(6,3) for the 9x3 layer (in-pipeline A/B, 3 rounds on one box: 9x3 131 ->
 // 122 us, step 260k -> 264k; F(4,3) on 39x12 tiles 140 us, F(3,3) spills):
 // 8 planes of the 39 x 6 tile's single column group, 4 waves of 16 output
-// channels each, 96 accumulator VGPRs
-#define AA_WG_CFGS(X) X(9, 64, 3, 1, 4, 3, 1, 39, 6, 0, 6, 1, 2)
+// channels each, 96 accumulator VGPRs.  SLIDE 9 and 4 B sets (harness, bit-
+// identical outputs: 113.9 -> 105.1 us sliding, -> 103.9 us with the deeper B
+// ring; serial trace 110.4 -> ~104 us; profiles/r07/conv_wg_slide.txt)
+#define AA_WG_CFGS(X) X(9, 64, 3, 1, 4, 3, 1, 39, 6, 0, 6, 1, 4, 9)
 #endif
 
 // The fused tail (aa_conv_tail.h: the 1x3/128 -> 256 conv and the 1x1 head in
@@ -76,7 +80,7 @@ namespace aa {
 constexpr int TAIL_TH = 13, TAIL_TW = AA_TAIL_TW;
 
 static int wg_bn(int kh, int kw, int cin, int pool) {
-#define AA_WBN(KH, CIN, POOL, WM, WN, MF, NF, TH, TW, OCC, WO, NPASS, BD) \
+#define AA_WBN(KH, CIN, POOL, WM, WN, MF, NF, TH, TW, OCC, WO, NPASS, BD, SLIDE) \
     if (kw == 3 && kh == KH && cin == CIN && pool == POOL) return WN * NF * 16;
     AA_WG_CFGS(AA_WBN)
 #undef AA_WBN
@@ -84,7 +88,7 @@ static int wg_bn(int kh, int kw, int cin, int pool) {
 }
 // (WO, NPASS) of the Winograd instantiation serving a stage
 static void wg_form(int kh, int cin, int pool, int* wo, int* npass) {
-#define AA_WFORM(KH, CIN, POOL, WM, WN, MF, NF, TH, TW, OCC, WO, NPASS, BD) \
+#define AA_WFORM(KH, CIN, POOL, WM, WN, MF, NF, TH, TW, OCC, WO, NPASS, BD, SLIDE) \
     if (kh == KH && cin == CIN && pool == POOL) { *wo = WO; *npass = NPASS; return; }
     AA_WG_CFGS(AA_WFORM)
 #undef AA_WFORM

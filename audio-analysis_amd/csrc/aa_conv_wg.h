@@ -31,8 +31,9 @@
 // wrap (the planes have no halo along W), so the ds_read_b128 lane groups
 // are conflict-free.  Weights come per step (group g, pass, row kh, plane) as
 // [cout_pad][8 units] with aa_conv_x3.h's swizzle, loaded per wave straight
-// from global (L2) one step ahead -- waves meet only at the barriers around
-// each staging.
+// from global (L2) BD - 1 steps ahead -- waves meet only at the barriers around
+// each staging.  With SLIDE (below) the fragments are read once per plane and
+// then move through registers.
 #pragma once
 
 #include <type_traits>
@@ -197,9 +198,39 @@ __device__ __forceinline__ void wg_stage(char* patch, int oh0, int ow0, int Hin,
     }
 }
 
+// SLIDE (one column group per tile row, NP = 1): the MFMA steps run plane by
+// plane, the kernel rows inside, and a wave's A fragments slide down the plane
+// in registers instead of being read from LDS at every row.  Fragment i's lane
+// r holds the output pixel p = MF r + i (interleaved, not 16 i + r), so at row
+// kh it needs the plane's pixel row MF r + i + kh: the fragment set R_m (lane
+// r: row MF r + m) serves fragment i at row kh = m - i, and R_(m + MF) is R_m
+// moved down one lane within each 16-lane row -- one DPP row_shl:1 per dword,
+// nothing to carry between fragments.  The lanes a shift leaves empty (zero)
+// stand for rows >= 16 MF > PH - 1, which only padding pixels (p >= TP, never
+// stored) read.  Per (group, plane) MF hi / lo pairs come from LDS instead of
+// MF KH.  SLIDE = S reads the plane again every S rows, KH: once.
+//
+// The weights of step s = ((g NPASS + pass) KH + kh) PPS + el stay where
+// pack_wg put them; only the order of the visits changes, and every
+// accumulator still sums (g, kh) ascending: results are bit-identical.
+// wg_slide_s: the step visited v-th in the plane-major order.
+template <int KH, int PPS>
+__host__ __device__ constexpr int wg_slide_s(int v) {
+    const int pi = v / (KH * PPS), t = v % (KH * PPS);
+    return (pi * KH + t % KH) * PPS + t / KH;
+}
+__device__ __forceinline__ bf16x8 wg_row_shl1(bf16x8 x) {
+    typedef __attribute__((ext_vector_type(4))) int i32x4;
+    i32x4 v = __builtin_bit_cast(i32x4, x);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] = __builtin_amdgcn_update_dpp(0, v[k], 0x101, 0xf, 0xf, true);  // row_shl:1
+    return __builtin_bit_cast(bf16x8, v);
+}
+
 // DIAG (tools/conv_bench_x3.hip only): bit 0 skips the staging, bit 1 the MFMA steps
 template <int KH, int CIN, int WM, int WN, int MF, int NF, int POOL, int TH, int TW, int OCC = 0,
-          bool IN_SPLIT = false, bool OUT_SPLIT = false, int DIAG = 0, int WO = 2, int NPASS = 1, int BD = 2>
+          bool IN_SPLIT = false, bool OUT_SPLIT = false, int DIAG = 0, int WO = 2, int NPASS = 1, int BD = 2,
+          int SLIDE = 0>
 __global__ __launch_bounds__(WM * WN * 64)
 __attribute__((amdgpu_waves_per_eu(OCC ? OCC : 1, OCC ? OCC : 8)))
 void conv_wg(const float* __restrict__ in, int Hin, int Win, const bf16* __restrict__ wt,
@@ -213,7 +244,8 @@ void conv_wg(const float* __restrict__ in, int Hin, int Win, const bf16* __restr
     // BD: B fragment sets in flight (the next BD - 1 steps' weights load under
     // this step's MFMAs); a runtime row loop needs the set of a step fixed by
     // its plane slot
-    static_assert(BD >= 2 && ((A / NPASS) % 2 != 0 || (A / NPASS) % BD == 0), "B ring depth divides the pass");
+    // (SLIDE unrolls every step and takes the set from the step's global index: any depth)
+    static_assert(BD >= 2 && (SLIDE > 0 || (A / NPASS) % 2 != 0 || (A / NPASS) % BD == 0), "B ring depth divides the pass");
     static_assert(TW % WO == 0 && TH % POOL == 0 && TW % POOL == 0, "group- and pool-aligned tile");
     constexpr int NP = TW / WO;  // output column groups per tile row
     constexpr int TP = TH * NP;  // group-pixels per tile
@@ -225,6 +257,8 @@ void conv_wg(const float* __restrict__ in, int Hin, int Win, const bf16* __restr
     constexpr int PV = PH * NP;  // group-pixels per plane
     constexpr int NG = CIN / 32;
     constexpr int NSTEP = NG * NPASS * KH * PPS;  // (group, pass, kh, plane of the pass)
+    static_assert(SLIDE == 0 || (NP == 1 && WM == 1 && PH <= MF * 16),
+                  "sliding A: one column group per row, one wave over the plane's rows");
     constexpr int SLICE = BN * 64;      // bf16 elements of one step's slice
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* patch = smem;
@@ -311,6 +345,73 @@ void conv_wg(const float* __restrict__ in, int Hin, int Win, const bf16* __restr
         }
     };
 
+    // SLIDE: the v-th visited step, (plane slot el, row kh) of its pass.  Its A
+    // fragments R_kh .. R_(kh + MF - 1) are in registers (ring slot m % (MF + 1),
+    // one ring per reload generation); under its MFMAs it prepares the next
+    // visit's: R_(kh + MF) shifted out of R_kh, or, where the next visit starts
+    // a plane or a reload, that visit's MF fragments read from LDS.  The first
+    // visit of a pass reads its own.
+    struct ASet {
+        bf16x8 h, l;
+    };
+    ASet Ar[2][MF + 1];
+    const int srow = MF * (lane & 15);  // the pixel row of the lane in R_0
+    // R_m's hi and lo addresses inside a plane (rows past the plane feed padding
+    // pixels only); the plane's base is a multiple of 128 B and goes into the
+    // reads' immediate offset, so planes share these registers
+    auto slide_ofs = [&](int m) {
+        const int row = min(srow + m, PH - 1);
+        return row * 128 + (((row + q) & 7) << 4);
+    };
+    int sofs[MF], sofl[MF];
+#pragma unroll
+    for (int i = 0; i < MF; ++i) {
+        sofs[i] = slide_ofs(i);
+        sofl[i] = sofs[i] ^ 64;
+    }
+    auto rd_slide = [&](ASet& r, int el, int m) {
+        const int ah = m < MF ? sofs[m < MF ? m : 0] : slide_ofs(m);
+        const int al = m < MF ? sofl[m < MF ? m : 0] : ah ^ 64;
+        r.h = *reinterpret_cast<const bf16x8*>(patch + el * PV * 128 + ah);
+        r.l = *reinterpret_cast<const bf16x8*>(patch + el * PV * 128 + al);
+    };
+    auto slide_step = [&](auto bc, auto vc, auto tc, auto ec) {
+        constexpr int e = decltype(ec)::value;
+        constexpr int b = decltype(bc)::value;
+        constexpr int v = decltype(vc)::value;
+        constexpr int t = decltype(tc)::value;  // visit within the pass
+        constexpr int S = SLIDE > 0 ? SLIDE : 1, RL = (KH + S - 1) / S;
+        constexpr int el = t / KH, kh = t % KH, gen = (el * RL + kh / S) & 1;
+        constexpr bool more = t + 1 < KH * PPS;
+        constexpr int nel = (t + 1) / KH, nkh = (t + 1) % KH, ngen = (nel * RL + nkh / S) & 1;
+        constexpr bool reload = more && nkh % S == 0;
+        BSet& cur = Bq[b];
+        if constexpr (v + BD - 1 < NSTEP) read_b(Bq[(b + BD - 1) % BD], wg_slide_s<KH, PPS>(v + BD - 1));
+        if constexpr (t == 0) {
+#pragma unroll
+            for (int i = 0; i < MF; ++i) rd_slide(Ar[gen][i], el, i);
+        }
+        if constexpr (AA_PIN_WG & 1) __builtin_amdgcn_sched_barrier(0);
+        wg_static_for<0, MF>([&](auto ic) {
+            constexpr int i = decltype(ic)::value;
+            const ASet& a = Ar[gen][(kh + i) % (MF + 1)];
+            if constexpr (reload) rd_slide(Ar[ngen][(nkh + i) % (MF + 1)], nel, nkh + i);
+            if constexpr (AA_PIN_WG & 2) __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int j = 0; j < NF; ++j) {
+                acc[e][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cur.h[j], a.h, acc[e][i][j], 0, 0, 0);
+                acc[e][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cur.l[j], a.h, acc[e][i][j], 0, 0, 0);
+                acc[e][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cur.h[j], a.l, acc[e][i][j], 0, 0, 0);
+            }
+            if constexpr (i == 0 && more && !reload) {
+                // R_kh has fed its last MFMAs: the next row's last fragment
+                ASet& n = Ar[gen][(kh + MF) % (MF + 1)];
+                n.h = wg_row_shl1(a.h);
+                n.l = wg_row_shl1(a.l);
+            }
+        });
+    };
+
     // one input value quad (4 channels of group g) of pixel (gh, gw), in f32
     // (buffer loads: the resource based at the window (64-bit), the pixel in the
     // lane's 32-bit offset -- any batch size, one window < 2 GiB)
@@ -332,7 +433,7 @@ void conv_wg(const float* __restrict__ in, int Hin, int Win, const bf16* __restr
 
 #pragma unroll
     for (int k = 0; k < BD - 1; ++k)
-        if (k < NSTEP) read_b(Bq[k], k);  // their latency hides behind the first staging
+        if (k < NSTEP) read_b(Bq[k], SLIDE ? wg_slide_s<KH, PPS>(k) : k);  // their latency hides behind the first staging
     wg_static_for<0, NG>([&](auto gc) {
         constexpr int g = decltype(gc)::value;
         wg_static_for<0, NPASS>([&](auto pc) {
@@ -342,7 +443,15 @@ void conv_wg(const float* __restrict__ in, int Hin, int Win, const bf16* __restr
             wg_stage<WO, PPS, pass * PPS, NP, PV, NTHR, (DIAG & 1) ? 0 : PV * 8>(patch, oh0, ow0, Hin, Win, g, load4);
             __syncthreads();
             if constexpr (AA_WG_PRIO > 0) __builtin_amdgcn_s_setprio(AA_WG_PRIO);  // (A/B knob, as AA_X3_PRIO)
-            if constexpr ((DIAG & 2) == 0) {
+            if constexpr ((DIAG & 2) == 0 && SLIDE > 0) {
+                // plane-major, rows inside, all unrolled: the B set by the visit's index
+                constexpr int vb = (g * NPASS + pass) * KH * PPS;
+                wg_static_for<0, KH * PPS>([&](auto tc) {
+                    constexpr int t = decltype(tc)::value;
+                    constexpr std::integral_constant<int, pass * PPS + t / KH> ec{};
+                    slide_step(std::integral_constant<int, (vb + t) % BD>{}, std::integral_constant<int, vb + t>{}, tc, ec);
+                });
+            } else if constexpr ((DIAG & 2) == 0) {
                 if constexpr (PPS % 2 == 0) {
                     // an even count of steps per row: the B sets alternate the same way every row
                     for (int kh = 0; kh < KH; ++kh) {
@@ -388,7 +497,7 @@ void conv_wg(const float* __restrict__ in, int Hin, int Win, const bf16* __restr
                 const int u = (wn % WNE) * NF * 4 + j * 4 + q;
 #pragma unroll
                 for (int i = 0; i < MF; ++i) {
-                    const int p = (wm * MF + i) * 16 + (lane & 15);
+                    const int p = SLIDE ? MF * (lane & 15) + i : (wm * MF + i) * 16 + (lane & 15);
                     if (p < TP) {
                         const int r = p / NP, jp = p - (p / NP) * NP;
                         const int px = r * TW + WO * jp;
