@@ -13,7 +13,8 @@ CSRC = PKG.parent / "csrc"
 INCLUDE = PKG.parent.parent / "include"
 LIB = PKG / "libaa.so"
 SOURCES = ["aa_api.cpp", "aa_frontend.hip", "aa_cnn.hip", "aa_scan.hip", "aa_signal.hip", "aa_flac.cpp",
-           "aa_vorbis.cpp", "aa_tracks.cpp", "aa_resample.hip", "aa_graph.hip", "aa_sosfilt.hip"]
+           "aa_vorbis.cpp", "aa_tracks.cpp", "aa_resample.hip", "aa_graph.hip", "aa_sosfilt.hip",
+           "aa_cacophony.hip"]
 ARCH = os.environ.get("AA_OFFLOAD_ARCH", "gfx950")
 # per-source flags: the FFT front end is written in scalar f32; SLP packing it
 # into v_pk_* ops needs paired SGPR constants and register shuffles that push
@@ -36,6 +37,10 @@ EXTRA_FLAGS = {"aa_frontend.hip": ["-fno-slp-vectorize"], "aa_signal.hip": ["-fn
                # name every rounding (__dmul_rn / __dadd_rn); this keeps the
                # host's one-step matrix (aa_sosfilt_plan) uncontracted too
                "aa_sosfilt.hip": ["-ffp-contract=off"]}
+# aa_cacophony.hip takes the default flags: the old cacophony index's window
+# product names its rounding (__dmul_rn), the f64 butterflies and the band
+# sums may contract into FMAs -- its gate is a bound on the band energies'
+# deviation from scipy's DCT, not their bits
 
 
 def hipcc() -> str:

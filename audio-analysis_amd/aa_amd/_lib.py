@@ -137,6 +137,13 @@ AA_SOS_LEVELS = 16
 AA_SOS_MAX_N = 1 << 28
 
 
+# the old cacophony index's geometry (include/aa.h AA_CI_*)
+AA_CI_N = 2048
+AA_CI_HOP = 1024
+AA_CI_BANDS = 10
+AA_CI_MAX_REC = 64
+
+
 class SosJob(C.Structure):
     _fields_ = [("src", C.c_int64), ("n", C.c_int64), ("dst", C.c_int64), ("n_sections", C.c_int32),
                 ("n_levels", C.c_int32), ("sos", C.c_double * 12), ("p", C.c_double * 16),
@@ -231,6 +238,13 @@ _SIGS = {
     "aa_sn_stage_time": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "aa_sn_components_from_mask": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t,
                                              C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "aa_ci_n_frames": (C.c_int64, [C.c_int64]),
+    "aa_ci_create": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "aa_ci_plan": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "aa_ci_destroy": (C.c_int, [C.c_void_p]),
+    "aa_ci_workspace_bytes": (C.c_size_t, [C.POINTER(C.c_int64), C.c_int32]),
+    "aa_ci_run": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32,
+                            C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "aa_flac_info": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(FlacInfo)]),
     "aa_flac_decode": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
     "aa_vorbis_info": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(VorbisInfo)]),

@@ -327,8 +327,10 @@ def main(argv=None):
     init_logging()
     t0 = time.time()
     if args.old_cacophony_index:
-        raise NotImplementedError("--old-cacophony-index (ffmpeg/opusdec DCT index) is out of scope")
-    summary = examine(args.file, args.bird_model, analyse_tracks=args.analyse_tracks)
+        from . import cacophony_index
+        summary = cacophony_index.calculate(args.file)
+    else:
+        summary = examine(args.file, args.bird_model, analyse_tracks=args.analyse_tracks)
     summary["processing_time_seconds"] = round(time.time() - t0, 1)
     if args.meta_to_stdout:
         print(json.dumps(summary, sort_keys=True, indent=4))

@@ -25,6 +25,8 @@
  *   aa_pcm_s16_to_f32  load_recording's s16 -> f32  src/identify_tracks.py:49-62
  *   aa_resample_poly   load_recording's resample     src/identify_tracks.py:49-62
  *   aa_sn_*      signal_noise                       src/identify_tracks.py:650-706
+ *   aa_ci_*      get_ci_bins + calculate's frame    src/cacophony_index.py:53-97
+ *                  loop (the old cacophony index)
  *   aa_flac_*    load_recording's ffmpeg decode     src/identify_tracks.py:49-62
  *                  (FLAC; host memory, no GPU)
  *   aa_vorbis_*  load_recording's ffmpeg decode     src/identify_tracks.py:49-62
@@ -502,6 +504,57 @@ int aa_sn_stage_time(void* plan, int32_t stage, double* total_ms, int64_t* count
 int aa_sn_components_from_mask(void* plan, const uint64_t* mask, int64_t n_frames, void* workspace,
                                size_t workspace_bytes, aa_sn_component* out, int32_t max_out,
                                int32_t* n_out, void* stream);
+
+/* ---------------------------------------------------------------- old cacophony index */
+/* The frame loop of the old cacophony index (src/cacophony_index.py:53-97) on
+ * 16 kHz mono f32 samples: frames of AA_CI_N samples at hop AA_CI_HOP, frame f
+ * of a recording covering x[AA_CI_HOP (f + 1) .. AA_CI_HOP (f + 1) + AA_CI_N)
+ * (the first AA_CI_HOP samples are never read, every frame lies inside the
+ * recording); per frame the float64 window times the f32 samples (one
+ * rounding each), the unnormalised DCT-II y[k] = 2 sum s[n] cos(pi k (2n + 1)
+ * / (2 AA_CI_N)) (scipy.fftpack.dct) in float64, and the energy sum y[k]^2 of
+ * AA_CI_BANDS bands [edges[b], edges[b + 1]); per pair of neighbouring frames
+ * the number of bands whose energy more than halved or more than doubled.
+ * The percentile scoring of those points stays on the host
+ * (aa_amd/cacophony_index.py). */
+#define AA_CI_N 2048
+#define AA_CI_HOP 1024
+#define AA_CI_BANDS 10
+#define AA_CI_MAX_REC 64         /* recordings per aa_ci_run */
+#define AA_CI_MAX_SAMPLES 1073741824 /* samples per recording, 2^30 */
+
+/* Frames of a recording of n samples: len(range(1024, n - 3072, 1024)), 0 for
+ * n <= 4096.  Host only. */
+int64_t aa_ci_n_frames(int64_t n_samples);
+/* window: host float64 [AA_CI_N] (numpy.hanning(2048)); edges: host int32
+ * [AA_CI_BANDS + 1] (numpy.logspace(log10(25), log10(2048), num=11,
+ * dtype=int)), non-decreasing within [0, AA_CI_N] (AA_ERR_INVALID otherwise,
+ * before any HIP call).  Both are the caller's data, so numpy's bits and its
+ * integer truncation stay numpy's.  aa_ci_plan: the plan alone, on the host
+ * (the aa_model_plan contract: the same checks, no device memory, no HIP
+ * call); aa_ci_run on it returns AA_ERR_INVALID. */
+int aa_ci_create(const double* window, const int32_t* edges, void** plan);
+int aa_ci_plan(const double* window, const int32_t* edges, void** plan);
+int aa_ci_destroy(void* plan);
+/* Workspace of one aa_ci_run over recordings of these lengths (HOST array)
+ * when bins_out is NULL: the band energies; 0 for no frames. */
+size_t aa_ci_workspace_bytes(const int64_t* lengths, int32_t n_rec);
+/* n_rec (0..AA_CI_MAX_REC) recordings in one device f32 buffer: recording k
+ * is pcm16k[offsets[k] .. offsets[k] + lengths[k]) (offsets, lengths: HOST
+ * arrays; any sample alignment).  With F_k = aa_ci_n_frames(lengths[k]):
+ * bins_out (device f64, may be NULL): F_k rows of AA_CI_BANDS energies per
+ * recording, the recordings' rows back to back; points_out (device int32):
+ * max(F_k - 1, 0) values per recording, back to back -- no comparison crosses
+ * a recording's boundary.  Two launches (ci_bands: one workgroup per frame of
+ * the whole batch; ci_points); the band sums are reduced in a fixed order,
+ * without atomics, so a run is bit-reproducible.
+ * Before any launch: null plan / pcm16k / offsets / lengths / points_out,
+ * negative offsets or lengths, lengths > AA_CI_MAX_SAMPLES and n_rec outside
+ * 0..AA_CI_MAX_REC are AA_ERR_INVALID; with bins_out NULL, a null, unaligned
+ * (8 bytes) or short workspace is AA_ERR_WORKSPACE.  n_rec == 0 and
+ * recordings without a frame are AA_OK.  Allocates nothing; capturable. */
+int aa_ci_run(void* plan, const float* pcm16k, const int64_t* offsets, const int64_t* lengths, int32_t n_rec,
+              void* workspace, size_t workspace_bytes, double* bins_out, int32_t* points_out, void* stream);
 
 /* ---------------------------------------------------------------- FLAC decode */
 /* load_recording (src/identify_tracks.py:49-62) decodes through ffmpeg; these
