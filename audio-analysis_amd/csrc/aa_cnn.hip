@@ -16,8 +16,11 @@
 //     conv, global max, sigmoid), conv_generic / pool_dense (f32 VALU
 //     fallbacks for any other shape), track_mean, stage_decode;
 //   * the split-bf16 kernel families, each in its own header: aa_conv_x3.h
-//     (direct), aa_conv_wg.h (Winograd along W), aa_gconv.h (runtime-shaped),
-//     aa_conv_tail.h (last conv + head in one launch);
+//     (direct; it also holds the fragment helpers -- x3_mfma3, x3_frag_pixel,
+//     x3_bofs, x3_read_b, x3_stage_split, x3_step_jit -- and the epilogue
+//     x3_store that the next two share), aa_conv_wg.h (Winograd along W),
+//     aa_conv_tail.h (last conv + head in one launch), aa_gconv.h
+//     (runtime-shaped; also built into aa_graph.hip, so it keeps its own);
 //   * aa_cnn_plan.h: Stage, Model and the host-only planner (layer list ->
 //     stages with packed weight images), over aa_cnn_tiles.h (tile tables)
 //     and aa_cnn_pack.h (weight layouts);

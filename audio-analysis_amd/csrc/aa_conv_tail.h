@@ -4,7 +4,7 @@
 // max, for the reference family's model shape (src/identify_tracks.py:302-327:
 // conv 1x3 -> 256, conv 1x1 -> labels, GlobalMaxPool2D, sigmoid).  Included
 // by aa_cnn.hip after aa_conv_x3.h (shares its swizzle, weight packing, the
-// grouped-split staging and x3_wload).
+// grouped-split stager x3_stage_split, x3_read_b, x3_step_jit and x3_mfma3).
 //
 // Separately the conv writes 13 x 20 x 256 f32 per window to HBM and the head
 // reads it back (two launches plus the head's partial-max pass); here:
@@ -69,56 +69,25 @@ __global__ __launch_bounds__(TAIL_NW * 64) void conv_tail_x3(
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63, q = lane >> 4;
 
-    // ---- stage every channel group's patch image (grouped-split input) ----
-    {
-        const __amdgpu_buffer_rsrc_t ars = x3_wrsrc(reinterpret_cast<const char*>(in) + (size_t)n * Hin * Win * CIN * 4);
-        constexpr int UNITS = PH * PW * 8;
-        for (int i0 = wave * 64; i0 < UNITS; i0 += NTHR) {
-            const int idx = i0 + lane;
-            if (idx < UNITS) {
-                const int pix = idx >> 3, slot = idx & 7;
-                const int R = pix / PW, C = pix - R * PW;
-                const int u = (slot - R * TW - C) & 7;
-                const int gh = min(oh0 + R, Hin - 1), gw = min(ow0 + C, Win - 1);
-#pragma unroll
-                for (int g = 0; g < NG; ++g)
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(
-                        ars, (__attribute__((address_space(3))) void*)(patch + g * GIMG + i0 * 16), 16,
-                        (gh * Win + gw) * (CIN * 4) + u * 16, g * 128, 0, 0);
-            }
-        }
-    }
+    // ---- stage every channel group's patch image (grouped-split input), one
+    // wait for all of them below ----
+    x3_stage_split<NG, CIN, PH, PW, TW, TAIL_NW>(smem, in, n, Hin, Win, oh0, ow0, 0, wave, lane);
 
     // per-lane fragment geometry (aa_conv_x3.h): pixel fragment i, B rows of this wave
     int abase[MF], aph[MF];
 #pragma unroll
     for (int i = 0; i < MF; ++i) {
-        int p = i * 16 + (lane & 15);
-        // padding rows (computed, never used): the pixel 16 k back, whose
-        // swizzle slot is the lane's own (no second address on a busy slot)
-        if (p >= TP) p = max(p - 16 * ((p - TP) / 16 + 1), 0);
+        const int p = x3_frag_pixel(i * 16 + (lane & 15), TP);
         const int r = p / TW, c = p - (p / TW) * TW;
         abase[i] = (r * PW + c) * 128;
         aph[i] = p + q;
     }
     int bofs[2];
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int row = wave * 32 + j * 16 + (lane & 15);
-        bofs[j] = row * 128 + (((q + row) & 7) << 4);
-    }
+    for (int j = 0; j < 2; ++j) bofs[j] = x3_bofs(wave * 32 + j * 16 + (lane & 15), q);
     const __amdgpu_buffer_rsrc_t wrs = x3_wrsrc(wt);
-    struct BSet {
-        bf16x8 h[2], l[2];
-    };
-    auto read_b = [&](BSet& b, int s) {
-        const int soff = __builtin_amdgcn_readfirstlane(s * SLICE * 2);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            b.h[j] = x3_wload(wrs, bofs[j], soff);
-            b.l[j] = x3_wload(wrs, bofs[j] ^ 64, soff);
-        }
-    };
+    typedef X3BSet<2> BSet;
+    auto read_b = [&](BSet& b, int s) { x3_read_b(b, wrs, bofs, __builtin_amdgcn_readfirstlane(s * SLICE * 2)); };
     f32x4 acc[MF][2];
 #pragma unroll
     for (int i = 0; i < MF; ++i) acc[i][0] = acc[i][1] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -134,30 +103,14 @@ __global__ __launch_bounds__(TAIL_NW * 64) void conv_tail_x3(
     __syncthreads();
 
     auto step = [&](int s) {
-        BSet& cur = Bq[s % BD];
         const int g = s / NTAP, t = s - (s / NTAP) * NTAP;
         if (s + BD - 1 < NSTEP) read_b(Bq[(s + BD - 1) % BD], s + BD - 1);
         const int kh = t / KW, kw = t - (t / KW) * KW;
         const int toff = g * GIMG + (kh * PW + kw) * 128, tv = kh * TW + kw;
-        bf16x8 h2[2], l2[2];
-        auto rd = [&](int i, int k) {
+        x3_step_jit<MF, 2, true>(acc, Bq[s % BD], [&](int i, int k) {
             const int a = abase[i] + toff + (((aph[i] + tv) & 7) << 4);
-            h2[k] = *reinterpret_cast<const bf16x8*>(patch + a);
-            l2[k] = *reinterpret_cast<const bf16x8*>(patch + (a ^ 64));
-        };
-        rd(0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int i = 0; i < MF; ++i) {
-            if (i + 1 < MF) rd(i + 1, (i + 1) & 1);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cur.h[j], h2[i & 1], acc[i][j], 0, 0, 0);
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cur.l[j], h2[i & 1], acc[i][j], 0, 0, 0);
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cur.h[j], l2[i & 1], acc[i][j], 0, 0, 0);
-            }
-        }
+            return *reinterpret_cast<const bf16x8*>(patch + (a ^ (64 * k)));
+        });
     };
 #pragma unroll
     for (int s = 0; s < NSTEP; ++s) step(s);
@@ -193,9 +146,8 @@ __global__ __launch_bounds__(TAIL_NW * 64) void conv_tail_x3(
         const bf16x8 xl = __builtin_bit_cast(bf16x8, make_uint4(l[0], l[1], l[2], l[3]));
 #pragma unroll
         for (int lf = 0; lf < 2; ++lf) {
-            f32x4 d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(whh[lf], xh, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-            d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(whl[lf], xh, d, 0, 0, 0);
-            D[i][lf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(whh[lf], xl, d, 0, 0, 0);
+            D[i][lf] = f32x4{0.f, 0.f, 0.f, 0.f};
+            x3_mfma3(D[i][lf], whh[lf], whl[lf], xh, xl);
         }
     }
     // ---- partial sums of the 8 waves in a fixed order ----

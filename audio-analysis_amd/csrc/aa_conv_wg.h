@@ -1,6 +1,7 @@
 // Split-bf16 convolution with a Winograd F(WO, 3) transform along W
 // (AA_PREC_BF16X3, kernel width 3), included by aa_cnn.hip after
-// aa_conv_x3.h (shares bf_hi/bf_lo, the grouped-split layout and x3_store).
+// aa_conv_x3.h (shares bf_hi/bf_lo, the grouped-split layout, the fragment
+// helpers x3_frag_pixel / x3_read_b / x3_step_jit / x3_mfma3 and x3_store).
 //
 // A kernel-width-3 conv computes, per output row, y_k = sum_t g_t d_{k+t}
 // along W.  F(WO, 3) produces WO adjacent outputs from A = WO + 2 inputs with
@@ -263,7 +264,7 @@ void conv_wg(const float* __restrict__ in, int Hin, int Win, const bf16* __restr
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* patch = smem;
 
-    const BlockPos bp = x3_block<true>();
+    const BlockPos bp = x3_block();
     const int n = bp.n, cb = bp.cb;
     const int th = bp.tile / tiles_w, tw = bp.tile - (bp.tile / tiles_w) * tiles_w;
     const int oh0 = th * TH, ow0 = tw * TW;
@@ -275,18 +276,14 @@ void conv_wg(const float* __restrict__ in, int Hin, int Win, const bf16* __restr
     int abase[MF], aph[MF];
 #pragma unroll
     for (int i = 0; i < MF; ++i) {
-        int p = (wm * MF + i) * 16 + (lane & 15);
-        // padding rows (computed, never stored): the pixel 16 k rows back, whose
-        // swizzle slot is the lane's own -- a padding lane reading pixel 0 put a
-        // second address on a busy slot of its ds_read_b128 group (the 9x3
-        // layer's MFMA loop: 6.5 M of its 7.5 M bank-conflict cycles per launch)
-        if (p >= TP) p = max(p - 16 * ((p - TP) / 16 + 1), 0);
+        const int p = x3_frag_pixel((wm * MF + i) * 16 + (lane & 15), TP);
         abase[i] = p * 128;
         aph[i] = p + q;
     }
     int bofs[NF];
 #pragma unroll
     for (int j = 0; j < NF; ++j) {
+        // x3_bofs, kept inline: as a call it changes this kernel's instruction stream
         const int row = wn * NF * 16 + j * 16 + (lane & 15);
         bofs[j] = row * 128 + (((q + row) & 7) << 4);
     }
@@ -301,48 +298,24 @@ void conv_wg(const float* __restrict__ in, int Hin, int Win, const bf16* __restr
 #pragma unroll
             for (int j = 0; j < NF; ++j) acc[e][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    struct BSet {
-        bf16x8 h[NF], l[NF];
-    };
+    typedef X3BSet<NF> BSet;
     BSet Bq[BD];
     auto read_b = [&](BSet& b, int s) {
-        const int soff = __builtin_amdgcn_readfirstlane((int)((cb * SLICE + s * step_stride) * 2));
-#pragma unroll
-        for (int j = 0; j < NF; ++j) {
-            b.h[j] = x3_wload(wrs, bofs[j], soff);
-            b.l[j] = x3_wload(wrs, bofs[j] ^ 64, soff);
-        }
+        x3_read_b(b, wrs, bofs, __builtin_amdgcn_readfirstlane((int)((cb * SLICE + s * step_stride) * 2)));
     };
     // one step: plane e (slot el of the staged pass) at row offset kh, B of
-    // this step in `cur`, the next step's B loaded into `nxt` under this
-    // step's MFMAs; A fragments just in time, two in flight
-    // bc: the step's B set (s % BD, known at compile time)
+    // this step in Bq[b] (b = s % BD, known at compile time), the B of step
+    // s + BD - 1 loaded under this step's MFMAs; A fragments just in time
     auto step = [&](auto bc, int s, int kh, auto ec, auto elc) {
         constexpr int e = decltype(ec)::value;
         constexpr int el = decltype(elc)::value;
         constexpr int b = decltype(bc)::value;
-        BSet& cur = Bq[b];
         if (s + BD - 1 < NSTEP) read_b(Bq[(b + BD - 1) % BD], s + BD - 1);
         const int pofs = el * PV * 128 + kh * NP * 128, tv = kh * NP;
-        bf16x8 h2[2], l2[2];
-        auto rd = [&](int i, int k) {
+        x3_step_jit<MF, NF, true>(acc[e], Bq[b], [&](int i, int k) {
             const int a = pofs + abase[i] + (((aph[i] + tv) & 7) << 4);
-            h2[k] = *reinterpret_cast<const bf16x8*>(patch + a);
-            l2[k] = *reinterpret_cast<const bf16x8*>(patch + (a ^ 64));
-        };
-        rd(0, 0);
-        if constexpr (AA_PIN_WG & 1) __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int i = 0; i < MF; ++i) {
-            if (i + 1 < MF) rd(i + 1, (i + 1) & 1);
-            if constexpr (AA_PIN_WG & 2) __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int j = 0; j < NF; ++j) {
-                acc[e][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cur.h[j], h2[i & 1], acc[e][i][j], 0, 0, 0);
-                acc[e][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cur.l[j], h2[i & 1], acc[e][i][j], 0, 0, 0);
-                acc[e][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cur.h[j], l2[i & 1], acc[e][i][j], 0, 0, 0);
-            }
-        }
+            return *reinterpret_cast<const bf16x8*>(patch + (a ^ (64 * k)));
+        });
     };
 
     // SLIDE: the v-th visited step, (plane slot el, row kh) of its pass.  Its A
@@ -391,18 +364,14 @@ void conv_wg(const float* __restrict__ in, int Hin, int Win, const bf16* __restr
 #pragma unroll
             for (int i = 0; i < MF; ++i) rd_slide(Ar[gen][i], el, i);
         }
-        if constexpr (AA_PIN_WG & 1) __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_sched_barrier(0);
         wg_static_for<0, MF>([&](auto ic) {
             constexpr int i = decltype(ic)::value;
             const ASet& a = Ar[gen][(kh + i) % (MF + 1)];
             if constexpr (reload) rd_slide(Ar[ngen][(nkh + i) % (MF + 1)], nel, nkh + i);
-            if constexpr (AA_PIN_WG & 2) __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int j = 0; j < NF; ++j) {
-                acc[e][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cur.h[j], a.h, acc[e][i][j], 0, 0, 0);
-                acc[e][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cur.l[j], a.h, acc[e][i][j], 0, 0, 0);
-                acc[e][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cur.h[j], a.l, acc[e][i][j], 0, 0, 0);
-            }
+            for (int j = 0; j < NF; ++j) x3_mfma3(acc[e][i][j], cur.h[j], cur.l[j], a.h, a.l);
             if constexpr (i == 0 && more && !reload) {
                 // R_kh has fed its last MFMAs: the next row's last fragment
                 ASet& n = Ar[gen][(kh + MF) % (MF + 1)];
@@ -442,7 +411,7 @@ void conv_wg(const float* __restrict__ in, int Hin, int Win, const bf16* __restr
             // ---- stage (group g, pass) ----
             wg_stage<WO, PPS, pass * PPS, NP, PV, NTHR, (DIAG & 1) ? 0 : PV * 8>(patch, oh0, ow0, Hin, Win, g, load4);
             __syncthreads();
-            if constexpr (AA_WG_PRIO > 0) __builtin_amdgcn_s_setprio(AA_WG_PRIO);  // (A/B knob, as AA_X3_PRIO)
+            __builtin_amdgcn_s_setprio(1);  // (as in conv_x3)
             if constexpr ((DIAG & 2) == 0 && SLIDE > 0) {
                 // plane-major, rows inside, all unrolled: the B set by the visit's index
                 constexpr int vb = (g * NPASS + pass) * KH * PPS;
@@ -477,7 +446,7 @@ void conv_wg(const float* __restrict__ in, int Hin, int Win, const bf16* __restr
                     });
                 }
             }
-            if constexpr (AA_WG_PRIO > 0) __builtin_amdgcn_s_setprio(0);
+            __builtin_amdgcn_s_setprio(0);
         });
     });
     __syncthreads();  // planes no longer needed: the f32 tile reuses LDS

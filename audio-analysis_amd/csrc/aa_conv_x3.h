@@ -38,54 +38,6 @@ namespace aa {
 
 constexpr int X3_CG = 32;  // channels per staged group
 
-// Build switches kept for in-pipeline A/B runs (tools/ab_build.py AB_DEFS):
-// AA_X3_XSPLIT: the fused first layer's log-mel patch split into bf16 hi / lo
-// once per element as it is staged, instead of once per tap read;
-// AA_X3_REMAP: XCD-aware block order (x3_block) for conv_x3 as for conv_wg.
-#ifndef AA_X3_XSPLIT
-#define AA_X3_XSPLIT 1
-#endif
-#ifndef AA_X3_REMAP
-#define AA_X3_REMAP 1
-#endif
-// AA_F1_KPACK: the fused first layer's 27 split products (hi.hi, hi.lo,
-// lo.hi over 9 taps) in 2 MFMAs instead of 3; AA_X3_SCALAR_SPLIT: its
-// activation / split in scalar f32 ops (packed f32 VALU costs extra issue
-// beside MFMAs).  Together: fused conv 136 -> 126 us in the pipeline
-// (harness 140 -> 132 us; each alone within the noise).
-#ifndef AA_F1_KPACK
-#define AA_F1_KPACK 1
-#endif
-#ifndef AA_X3_SCALAR_SPLIT
-#define AA_X3_SCALAR_SPLIT 1
-#endif
-
-// Scheduling pins for the kernels whose waves load their own B fragments
-// from global memory (conv_x3 with RING = false, conv_wg).  Bit 0: the next
-// step's fragment loads are issued before this step's MFMAs; bit 1: fragment
-// i+1's just-in-time A read before fragment i's MFMAs.  Without them the
-// scheduler sinks the prefetches down to their first use and the wave waits
-// out the L2 latency every step (s_waitcnt vmcnt(0) right after the issue,
-// tools/isa_stats.py).  In-pipeline A/B: fused first conv 153 -> 147 us,
-// Winograd 9x3 152 -> 138 us; the ring kernels (LDS-staged B, a barrier per
-// step) lose with either pin (3x3/64: 52 -> 58 / 71 us), so they stay unpinned.
-#ifndef AA_PIN_X3
-#define AA_PIN_X3 3
-#endif
-// MFMA steps at issue priority 1 (s_setprio) in conv_x3 and conv_wg: in-pipeline
-// A/B, 3 rounds on one box, step 259.2k -> 261.6k audio-s/s (both) -- the
-// other batch's front end and the co-resident blocks' staging VALU fill the
-// slots the matrix pipe leaves instead of delaying its issue
-#ifndef AA_X3_PRIO
-#define AA_X3_PRIO 1
-#endif
-#ifndef AA_WG_PRIO
-#define AA_WG_PRIO 1
-#endif
-#ifndef AA_PIN_WG
-#define AA_PIN_WG 3
-#endif
-
 template <int KH, int KW, int TH, int TW, bool FUSED>
 __host__ __device__ constexpr size_t x3_patch_bytes() {
     size_t b = (size_t)(TH + KH - 1) * (TW + KW - 1) * 128;
@@ -145,21 +97,15 @@ __device__ __forceinline__ void split2(float x0, float x1, uint32_t& hi, uint32_
 // for hi, its two halves back to f32 (shift / mask), two subtracts, one
 // packed conversion for lo.  The max is v_med3_f32(x, a x, +inf) through the
 // builtin: max(x, a x) for every non-NaN x (the inputs are MFMA results),
-// without the NaN canonicalisation a plain fmaxf adds, and -- unlike the
-// inline-asm v_max_f32 of round 5 -- visible to the hazard recognizer, which
-// pads the first VALU read of an MFMA result with the wait states the matrix
-// pipe needs (an asm read right behind the MFMA took stale registers in
-// the round-5 conv_wgf).  AA_X3_SCALAR_SPLIT 0: the multiply as one packed op.
+// without the NaN canonicalisation a plain fmaxf adds, and -- unlike an
+// inline-asm v_max_f32 -- visible to the hazard recognizer, which pads the
+// first VALU read of an MFMA result with the wait states the matrix pipe
+// needs.  Scalar multiplies: packed f32 VALU costs extra issue beside MFMAs.
 __device__ __forceinline__ void leaky_split2(float x0, float x1, float a, uint32_t& hi, uint32_t& lo) {
     typedef __attribute__((ext_vector_type(2))) float f2;
     typedef __attribute__((ext_vector_type(2))) __bf16 b2;
     constexpr float inf = __builtin_inff();
-#if AA_X3_SCALAR_SPLIT
     const float r0 = x0 * a, r1 = x1 * a;
-#else
-    const f2 r = f2{x0, x1} * a;
-    const float r0 = r.x, r1 = r.y;
-#endif
     const float o0 = __builtin_amdgcn_fmed3f(x0, r0, inf);
     const float o1 = __builtin_amdgcn_fmed3f(x1, r1, inf);
     hi = __builtin_bit_cast(uint32_t, __builtin_convertvector(f2{o0, o1}, b2));
@@ -181,19 +127,14 @@ __device__ __forceinline__ int x3_addr(int R, int C, int u, int PW, int TW) {
 // Renumber so each XCD works through a contiguous range of (window, tile,
 // channel block) with the channel block fastest: the blocks that stage the
 // same input patch (all channel blocks of a tile) and its neighbours (the
-// next tiles, which share the halo) meet in the same L2.  In-pipeline A/B:
-// the Winograd 9x3 kernel (two channel blocks per tile) gains a little; the
-// conv_x3 kernels lost 0.8 % of the step with it at first and gained 0.3 %
-// (3 of 3 rounds) after the later occupancy and first-layer changes, so they
-// remap too (AA_X3_REMAP).
+// next tiles, which share the halo) meet in the same L2.
 struct BlockPos {
     int tile, cb, n;
 };
-template <bool REMAP>
 __device__ __forceinline__ BlockPos x3_block() {
     const int gx = gridDim.x, gy = gridDim.y, G = gx * gy * gridDim.z;
     int L = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
-    if (REMAP && (G & 7) == 0) L = (L & 7) * (G >> 3) + (L >> 3);
+    if ((G & 7) == 0) L = (L & 7) * (G >> 3) + (L >> 3);
     BlockPos b;
     b.cb = L % gy;
     const int r = L / gy;
@@ -211,6 +152,104 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t x3_wrsrc(const void* wt) {
 }
 __device__ __forceinline__ bf16x8 x3_wload(__amdgpu_buffer_rsrc_t rs, int voff, int soff) {
     return __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff, 0));
+}
+
+// ---- fragment helpers shared by conv_wg and conv_tail_x3; conv_x3 below
+// uses x3_mfma3 and holds the rest inline (see the note above it) ----
+
+// The split product of one fragment pair: hi.hi, lo.hi, hi.lo in this order,
+// B as the first operand (every accumulator sums its products in this order:
+// the kernels' results are compared bit for bit)
+__device__ __forceinline__ void x3_mfma3(f32x4& acc, bf16x8 bh, bf16x8 bl, bf16x8 ah, bf16x8 al) {
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh, ah, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bl, ah, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh, al, acc, 0, 0, 0);
+}
+
+// The tile pixel (of TP) a fragment lane reads for pixel index p.  Padding
+// lanes (p >= TP: computed, never stored) take the pixel 16 k back, whose
+// swizzle slot is the lane's own -- a padding lane reading pixel 0 put a
+// second address on a busy slot of its ds_read_b128 group (the 9x3 layer's
+// MFMA loop: 6.5 M of its 7.5 M bank-conflict cycles per launch)
+__device__ __forceinline__ int x3_frag_pixel(int p, int TP) {
+    return p >= TP ? max(p - 16 * ((p - TP) / 16 + 1), 0) : p;
+}
+
+// byte offset of a lane's hi B unit (k-group q of output row `row`) in a
+// step's weight slice; lo: ^ 64
+__device__ __forceinline__ int x3_bofs(int row, int q) { return row * 128 + (((q + row) & 7) << 4); }
+
+// A wave's own B fragments of one step (NF x 16 output rows, hi and lo),
+// loaded straight from the packed weights in global memory (L2-resident);
+// soff: the step's slice base, wave-uniform
+template <int NF>
+struct X3BSet {
+    bf16x8 h[NF], l[NF];
+};
+template <int NF>
+__device__ __forceinline__ void x3_read_b(X3BSet<NF>& b, __amdgpu_buffer_rsrc_t wrs, const int (&bofs)[NF], int soff) {
+#pragma unroll
+    for (int j = 0; j < NF; ++j) {
+        b.h[j] = x3_wload(wrs, bofs[j], soff);
+        b.l[j] = x3_wload(wrs, bofs[j] ^ 64, soff);
+    }
+}
+
+// Stage NGS channel groups (g0 .. g0 + NGS - 1) of a PH x PW patch straight
+// from grouped-split activations, one swizzled 128-B-per-pixel image per
+// group (PH * PW * 128 bytes apart): LDS unit index i = pixel * 8 + slot; slot
+// holds unit (slot - R*TW - C) & 7 of pixel (R, C).  Out-of-image pixels read
+// a clamped (finite) pixel: they only feed discarded outputs.  Buffer loads:
+// the resource based at the window (64-bit, so any batch size), the group's
+// base in the SGPR offset, the pixel / unit in the lane's VGPR offset.  The
+// caller waits (s_waitcnt vmcnt) before the barrier that publishes the patch.
+template <int NGS, int CIN, int PH, int PW, int TW, int NW>
+__device__ __forceinline__ void x3_stage_split(char* patch, const float* in, int n, int Hin, int Win, int oh0, int ow0,
+                                               int g0, int wave, int lane) {
+    constexpr int UNITS = PH * PW * 8;
+    const __amdgpu_buffer_rsrc_t ars = x3_wrsrc(reinterpret_cast<const char*>(in) + (size_t)n * Hin * Win * CIN * 4);
+    for (int i0 = wave * 64; i0 < UNITS; i0 += NW * 64) {
+        const int idx = i0 + lane;
+        if (idx < UNITS) {
+            const int pix = idx >> 3, slot = idx & 7;
+            const int R = pix / PW, C = pix - R * PW;
+            const int u = (slot - R * TW - C) & 7;
+            const int gh = min(oh0 + R, Hin - 1), gw = min(ow0 + C, Win - 1);
+#pragma unroll
+            for (int k = 0; k < NGS; ++k)
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(
+                    ars, (__attribute__((address_space(3))) void*)(patch + k * (PH * PW * 128) + i0 * 16), 16,
+                    (gh * Win + gw) * (CIN * 4) + u * 16, (g0 + k) * 128, 0, 0);
+        }
+    }
+}
+
+// One MFMA step with the A fragments read just in time, two in flight:
+// fragment i+1's LDS read under fragment i's MFMAs (2 x 16 VGPRs instead of
+// 2 x MF x 8).  rd(i, k): the caller's address rule -- pixel fragment i's hi
+// (k = 0) or lo (k = 1) operand of this step.  PIN: scheduling barriers that
+// keep what the caller issued before the step (the next step's B loads) ahead
+// of its MFMAs and fragment i+1's read ahead of fragment i's MFMAs; without
+// them the scheduler sinks the prefetches down to their first use and the
+// wave waits out the latency every step.  For the kernels whose waves load
+// their own B from global memory; the ring kernels (LDS-staged B, a barrier
+// per step) lose with either pin and stay unpinned.
+template <int MF, int NF, bool PIN, typename Rd>
+__device__ __forceinline__ void x3_step_jit(f32x4 (&acc)[MF][NF], const X3BSet<NF>& cur, Rd&& rd) {
+    bf16x8 h2[2], l2[2];
+    h2[0] = rd(0, 0);
+    l2[0] = rd(0, 1);
+    if constexpr (PIN) __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int i = 0; i < MF; ++i) {
+        if (i + 1 < MF) {
+            h2[(i + 1) & 1] = rd(i + 1, 0);
+            l2[(i + 1) & 1] = rd(i + 1, 1);
+        }
+        if constexpr (PIN) __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int j = 0; j < NF; ++j) x3_mfma3(acc[i][j], cur.h[j], cur.l[j], h2[i & 1], l2[i & 1]);
+    }
 }
 
 // Epilogue shared by the split-bf16 kernels.  The f32 tile E holds TH*TW
@@ -251,10 +290,10 @@ __device__ __forceinline__ void x3_store(const float* E, const float* __restrict
                                          int cb, int oh0, int ow0, int Hout, int Wout, int cout_store, int act,
                                          float alpha, int tid = -1, const float4* bias_pre = nullptr) {
     // tid: the thread's index among the NTHR storing threads (default: the
-    // block's thread index; the producer waves of conv_x3pc pass their own,
-    // with the thread's bias quad loaded once (bias_pre, x3_store_bias):
-    // a bias load here would make the stores' s_waitcnt vmcnt also wait for
-    // every load the wave issued before it)
+    // block's thread index; a kernel whose storing waves are a subset of the
+    // block passes its own, with the thread's bias quad loaded once (bias_pre,
+    // x3_store_bias): a bias load here would make the stores' s_waitcnt vmcnt
+    // also wait for every load the wave issued before it)
     if (tid < 0) tid = threadIdx.x;
     constexpr int U = BN / 4;
     static_assert(U >= 8 && (U & (U - 1)) == 0, "a power-of-two count (>= 8) of units per pixel");
@@ -320,6 +359,12 @@ __device__ __forceinline__ void x3_store(const float* E, const float* __restrict
     }
 }
 
+// conv_x3 uses x3_mfma3 (instruction streams identical to the inline form) and
+// keeps its own inline lane geometry (x3_frag_pixel, x3_bofs), B set, split
+// stager and just-in-time step: x3_frag_pixel or x3_bofs alone changes the
+// streams of all 24 of its instantiations, and built on all of the helpers
+// the fused first conv measured 0.8 % slower.
+//
 // RING = false: no weight ring and no per-step barrier -- every wave loads
 // its own B fragments (its NF x 16 output-channel rows of the step) straight
 // from global memory (L2-resident weights) one step ahead, so waves only
@@ -361,7 +406,7 @@ void conv_x3(const float* __restrict__ in, int Hin, int Win, const bf16* __restr
     // (s_memtime) and hardware ids after the output, for timeline analysis
     unsigned long long ts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if constexpr (DIAG & 4096) ts[0] = __builtin_amdgcn_s_memtime();
-    const BlockPos bp = x3_block<AA_X3_REMAP != 0>();
+    const BlockPos bp = x3_block();
     const int n = bp.n, cb = bp.cb;
     const int th = bp.tile / tiles_w, tw = bp.tile - (bp.tile / tiles_w) * tiles_w;
     const int oh0 = th * TH, ow0 = tw * TW;
@@ -406,11 +451,7 @@ void conv_x3(const float* __restrict__ in, int Hin, int Win, const bf16* __restr
     // lane's fragment addresses for all 8 swizzle residues precomputed, so a
     // tap's A reads are a register plus an immediate offset (no per-read
     // address arithmetic in the fully unrolled tap loop)
-#ifdef AA_NO_AOFF
-    constexpr bool AOFF = false;
-#else
     constexpr bool AOFF = FUSED;
-#endif
     int aoff[AOFF ? MF : 1][8];
     if constexpr (AOFF) {
 #pragma unroll
@@ -487,15 +528,11 @@ void conv_x3(const float* __restrict__ in, int Hin, int Win, const bf16* __restr
         if (s + 1 < NSTEP) read_b(nxt, s + 1);
         if constexpr (!AJIT) {
             if (t + 1 < NTAP) read_a(nxt, t + 1);
-            if constexpr (!RING && (AA_PIN_X3 & 1)) __builtin_amdgcn_sched_barrier(0);
+            if constexpr (!RING) __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int i = 0; i < MF; ++i)
 #pragma unroll
-                for (int j = 0; j < NF; ++j) {
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cur.bh[j], cur.ah[i], acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cur.bl[j], cur.ah[i], acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cur.bh[j], cur.al[i], acc[i][j], 0, 0, 0);
-                }
+                for (int j = 0; j < NF; ++j) x3_mfma3(acc[i][j], cur.bh[j], cur.bl[j], cur.ah[i], cur.al[i]);
         } else {
             // A fragments just in time, two in flight: fragment i+1's LDS read
             // under fragment i's MFMAs (2 x 16 VGPRs instead of 2 x MF x 8)
@@ -513,17 +550,13 @@ void conv_x3(const float* __restrict__ in, int Hin, int Win, const bf16* __restr
                 }
             };
             rd(0, 0);
-            if constexpr (!RING && (AA_PIN_X3 & 1)) __builtin_amdgcn_sched_barrier(0);
+            if constexpr (!RING) __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int i = 0; i < MF; ++i) {
                 if (i + 1 < MF) rd(i + 1, (i + 1) & 1);
-                if constexpr (!RING && (AA_PIN_X3 & 2)) __builtin_amdgcn_sched_barrier(0);
+                if constexpr (!RING) __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int j = 0; j < NF; ++j) {
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cur.bh[j], h2[i & 1], acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cur.bl[j], h2[i & 1], acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cur.bh[j], l2[i & 1], acc[i][j], 0, 0, 0);
-                }
+                for (int j = 0; j < NF; ++j) x3_mfma3(acc[i][j], cur.bh[j], cur.bl[j], h2[i & 1], l2[i & 1]);
             }
         }
     };
@@ -541,27 +574,17 @@ void conv_x3(const float* __restrict__ in, int Hin, int Win, const bf16* __restr
     if constexpr (FUSED) {
         const int l32 = lane & 31, kg = lane >> 5;
         const int ch1 = 16 * ((l32 >> 2) & 1) + 4 * (l32 >> 3) + (l32 & 3);
-        if constexpr (AA_F1_KPACK) {
-            // the 27 products of a pixel (hi.hi, hi.lo, lo.hi over 9 taps) in the
-            // 32 k-slots of two MFMAs: MFMA 1 = wh.xh (k-group 0) and wh.xl
-            // (k-group 1) over taps 0-7; MFMA 2 = wl.xh over taps 0-7 (k-group
-            // 0) and wh8.xh8, wh8.xl8, wl8.xh8 (k-group 1)
-            float w9[9];
+        // the 27 products of a pixel (hi.hi, hi.lo, lo.hi over 9 taps) in the
+        // 32 k-slots of two MFMAs: MFMA 1 = wh.xh (k-group 0) and wh.xl
+        // (k-group 1) over taps 0-7; MFMA 2 = wl.xh over taps 0-7 (k-group
+        // 0) and wh8.xh8, wh8.xl8, wl8.xh8 (k-group 1)
+        float w9[9];
 #pragma unroll
-            for (int t = 0; t < 9; ++t) w9[t] = fc.w[ch1 * 9 + t];
+        for (int t = 0; t < 9; ++t) w9[t] = fc.w[ch1 * 9 + t];
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                f1_wa[j] = bf_hi(w9[j]);
-                f1_wal[j] = kg == 0 ? bf_lo(w9[j]) : j < 2 ? bf_hi(w9[8]) : j == 2 ? bf_lo(w9[8]) : (bf16)0.f;
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int tap = 8 * kg + j;
-                const float wv = fc.w[ch1 * 9 + min(tap, 8)];
-                f1_wa[j] = tap < 9 ? bf_hi(wv) : (bf16)0.f;
-                f1_wal[j] = tap < 9 ? bf_lo(wv) : (bf16)0.f;
-            }
+        for (int j = 0; j < 8; ++j) {
+            f1_wa[j] = bf_hi(w9[j]);
+            f1_wal[j] = kg == 0 ? bf_lo(w9[j]) : j < 2 ? bf_hi(w9[8]) : j == 2 ? bf_lo(w9[8]) : (bf16)0.f;
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r) f1_cb[r] = fc.b[16 * kg + r];
@@ -637,14 +660,14 @@ void conv_x3(const float* __restrict__ in, int Hin, int Win, const bf16* __restr
             }
         } else {
             // fused first layer (C_in = 1, 3x3 -> 32): log-mel patch (PH+2) x (PW+2)
-            // in LDS after the activation patch, then per 32 patch pixels three
-            // v_mfma_f32_32x32x16_bf16 (weights hi/lo x log-mel hi/lo, the 9 taps
-            // in k, the bias as C), activation, hi/lo into the swizzled patch
+            // in LDS after the activation patch, then per 32 patch pixels two
+            // v_mfma_f32_32x32x16_bf16 (weights hi/lo x log-mel hi/lo, the 27
+            // split products in k, the bias as C), activation, hi/lo into the
+            // swizzled patch
             constexpr int XW = PW + 2, XN = (PH + 2) * XW;
-            // X: the log-mel patch split once per element, bf16 hi in the low and
-            // bf16 lo in the high half of a dword (AA_X3_XSPLIT), else f32
-            float* X = reinterpret_cast<float*>(smem + (size_t)PH * PW * 128);
-            uint32_t* Xs = reinterpret_cast<uint32_t*>(X);
+            // Xs: the log-mel patch split once per element as it is staged, bf16
+            // hi in the low and bf16 lo in the high half of a dword
+            uint32_t* Xs = reinterpret_cast<uint32_t*>(smem + (size_t)PH * PW * 128);
             // buffer loads: the resource based at the window (64-bit, so any
             // batch size), the element in the lane's offset
             const int esz = fc.lm_f16 ? 2 : 4;
@@ -668,22 +691,16 @@ void conv_x3(const float* __restrict__ in, int Hin, int Win, const bf16* __restr
 #pragma unroll
                 for (int u = 0; u < XU; u += 2) {
                     const int idx = i0 + u * NTHR + threadIdx.x, idx2 = idx + NTHR;
-                    if constexpr (AA_X3_XSPLIT) {
-                        uint32_t h, l;
-                        split2(v[u], v[u + 1], h, l);
-                        if (idx < XN) Xs[idx] = __builtin_amdgcn_perm(l, h, 0x05040100u);     // hi | lo << 16
-                        if (idx2 < XN) Xs[idx2] = __builtin_amdgcn_perm(l, h, 0x07060302u);
-                    } else {
-                        if (idx < XN) X[idx] = v[u];
-                        if (idx2 < XN) X[idx2] = v[u + 1];
-                    }
+                    uint32_t h, l;
+                    split2(v[u], v[u + 1], h, l);
+                    if (idx < XN) Xs[idx] = __builtin_amdgcn_perm(l, h, 0x05040100u);     // hi | lo << 16
+                    if (idx2 < XN) Xs[idx2] = __builtin_amdgcn_perm(l, h, 0x07060302u);
                 }
             }
             const int l32 = lane & 31, kg = lane >> 5;
             const bf16x8 wa = f1_wa, wal = f1_wal;
             const f32x16 cb = f1_cb;
             const float ae = fc.alpha;  // host: act folded to a slope in [0, 1]
-            const int off0 = kg ? 2 * XW + 2 : 0;  // k-group 1 only needs tap 8 (j = 0)
             if constexpr (DIAG & 4096) ts[4] = __builtin_amdgcn_s_memtime();
             __syncthreads();
             if constexpr (DIAG & 4096) ts[5] = __builtin_amdgcn_s_memtime();
@@ -700,57 +717,25 @@ void conv_x3(const float* __restrict__ in, int Hin, int Win, const bf16* __restr
                 for (int u = 0; u < NU; ++u) {
                     pix[u] = min((g0 + NW * u) * 32 + l32, NPX - 1);
                     const int r = pix[u] / PW, c = pix[u] - r * PW;
-                    if constexpr (AA_F1_KPACK) {
-                        // taps 2k, 2k+1 -> one dword of MFMA 1's operand: their
-                        // hi halves in k-group 0, lo halves in k-group 1; MFMA 2
-                        // takes the same (k-group 0) or tap 8's hi, lo, hi
-                        const uint32_t* xp = Xs + r * XW + c;
-                        uint32_t xv[9];
+                    // taps 2k, 2k+1 -> one dword of MFMA 1's operand: their
+                    // hi halves in k-group 0, lo halves in k-group 1; MFMA 2
+                    // takes the same (k-group 0) or tap 8's hi, lo, hi
+                    const uint32_t* xp = Xs + r * XW + c;
+                    uint32_t xv[9];
 #pragma unroll
-                        for (int j = 0; j < 9; ++j) xv[j] = xp[(j / 3) * XW + j % 3];
-                        const uint32_t psel = kg ? 0x07060302u : 0x05040100u;
-                        uint4 b1, b2;
-                        b1.x = __builtin_amdgcn_perm(xv[1], xv[0], psel);
-                        b1.y = __builtin_amdgcn_perm(xv[3], xv[2], psel);
-                        b1.z = __builtin_amdgcn_perm(xv[5], xv[4], psel);
-                        b1.w = __builtin_amdgcn_perm(xv[7], xv[6], psel);
-                        b2.x = kg ? xv[8] : b1.x;
-                        b2.y = kg ? (xv[8] & 0xffffu) : b1.y;
-                        b2.z = kg ? 0u : b1.z;
-                        b2.w = kg ? 0u : b1.w;
-                        xh[u] = __builtin_bit_cast(bf16x8, b1);
-                        xl[u] = __builtin_bit_cast(bf16x8, b2);
-                    } else if constexpr (AA_X3_XSPLIT) {
-                        // taps 2k, 2k+1 of the pre-split patch -> one dword of
-                        // the hi fragment (low halves) and one of the lo (high halves)
-                        const uint32_t* xp = Xs + r * XW + c;
-                        uint32_t xv[8];
-                        xv[0] = xp[off0];
-#pragma unroll
-                        for (int j = 1; j < 8; ++j) xv[j] = xp[(j / 3) * XW + j % 3];
-                        uint4 hh, ll;
-                        hh.x = __builtin_amdgcn_perm(xv[1], xv[0], 0x05040100u);
-                        hh.y = __builtin_amdgcn_perm(xv[3], xv[2], 0x05040100u);
-                        hh.z = __builtin_amdgcn_perm(xv[5], xv[4], 0x05040100u);
-                        hh.w = __builtin_amdgcn_perm(xv[7], xv[6], 0x05040100u);
-                        ll.x = __builtin_amdgcn_perm(xv[1], xv[0], 0x07060302u);
-                        ll.y = __builtin_amdgcn_perm(xv[3], xv[2], 0x07060302u);
-                        ll.z = __builtin_amdgcn_perm(xv[5], xv[4], 0x07060302u);
-                        ll.w = __builtin_amdgcn_perm(xv[7], xv[6], 0x07060302u);
-                        xh[u] = __builtin_bit_cast(bf16x8, hh);
-                        xl[u] = __builtin_bit_cast(bf16x8, ll);
-                    } else {
-                        const float* xp = X + r * XW + c;
-                        float xv[8];
-                        xv[0] = xp[off0];
-#pragma unroll
-                        for (int j = 1; j < 8; ++j) xv[j] = xp[(j / 3) * XW + j % 3];
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) {
-                            xh[u][j] = bf_hi(xv[j]);
-                            xl[u][j] = bf_lo(xv[j]);
-                        }
-                    }
+                    for (int j = 0; j < 9; ++j) xv[j] = xp[(j / 3) * XW + j % 3];
+                    const uint32_t psel = kg ? 0x07060302u : 0x05040100u;
+                    uint4 b1, b2;
+                    b1.x = __builtin_amdgcn_perm(xv[1], xv[0], psel);
+                    b1.y = __builtin_amdgcn_perm(xv[3], xv[2], psel);
+                    b1.z = __builtin_amdgcn_perm(xv[5], xv[4], psel);
+                    b1.w = __builtin_amdgcn_perm(xv[7], xv[6], psel);
+                    b2.x = kg ? xv[8] : b1.x;
+                    b2.y = kg ? (xv[8] & 0xffffu) : b1.y;
+                    b2.z = kg ? 0u : b1.z;
+                    b2.w = kg ? 0u : b1.w;
+                    xh[u] = __builtin_bit_cast(bf16x8, b1);
+                    xl[u] = __builtin_bit_cast(bf16x8, b2);
                 }
                 f32x16 d[NU];
                 if constexpr (DIAG & 8192) {  // ablation: no first-layer MFMAs
@@ -759,18 +744,11 @@ void conv_x3(const float* __restrict__ in, int Hin, int Win, const bf16* __restr
                         d[u] = cb;
                         d[u][0] += __builtin_bit_cast(float, __builtin_bit_cast(uint4, xh[u]).x ^ __builtin_bit_cast(uint4, xl[u]).y);
                     }
-                } else if constexpr (AA_F1_KPACK) {
+                } else {
 #pragma unroll
                     for (int u = 0; u < NU; ++u) d[u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa, xh[u], cb, 0, 0, 0);
 #pragma unroll
                     for (int u = 0; u < NU; ++u) d[u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wal, xl[u], d[u], 0, 0, 0);
-                } else {
-#pragma unroll
-                for (int u = 0; u < NU; ++u) d[u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa, xh[u], cb, 0, 0, 0);
-#pragma unroll
-                for (int u = 0; u < NU; ++u) d[u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa, xl[u], d[u], 0, 0, 0);
-#pragma unroll
-                for (int u = 0; u < NU; ++u) d[u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wal, xh[u], d[u], 0, 0, 0);
                 }
 #pragma unroll
                 for (int u = 0; u < NU; ++u) {
@@ -831,16 +809,16 @@ void conv_x3(const float* __restrict__ in, int Hin, int Win, const bf16* __restr
         // output of a bottom tile with few valid rows)
         const bool wave_idle = !RING && oh0 + (wm * MF * 16) / TW >= Hout * POOL;
         if constexpr (DIAG & 4096) ts[1] = __builtin_amdgcn_s_memtime();
-        // AA_X3_PRIO (A/B knob): the wave's MFMA steps at a raised issue
-        // priority, so waves of co-resident blocks still staging (VALU) fill
-        // the slots the matrix pipe leaves instead of delaying its issue
-        if constexpr (AA_X3_PRIO > 0) __builtin_amdgcn_s_setprio(AA_X3_PRIO);
+        // the wave's MFMA steps at a raised issue priority, so waves of
+        // co-resident blocks still staging (VALU) fill the slots the matrix
+        // pipe leaves instead of delaying its issue
+        __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int t = 0; t < ((DIAG & 2) || wave_idle ? 0 : NTAP); t += 2) {
             step(F0, F1, g, t);
             if (t + 1 < NTAP) step(F1, F0, g, t + 1);
         }
-        if constexpr (AA_X3_PRIO > 0) __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_s_setprio(0);
         if constexpr (DIAG & 4096) ts[2] = __builtin_amdgcn_s_memtime();
     }
 #undef X3_GLDS

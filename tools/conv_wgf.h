@@ -75,7 +75,7 @@ void conv_wgf(const float* __restrict__ in, int Hin, int Win, const bf16* __rest
     char* patch = smem;
     uint32_t* Xs = reinterpret_cast<uint32_t*>(smem + (size_t)8 * PS * 128);
 
-    const BlockPos bp = x3_block<true>();
+    const BlockPos bp = x3_block();
     const int n = bp.n, cb = bp.cb;
     const int th = bp.tile / tiles_w, tw = bp.tile - (bp.tile / tiles_w) * tiles_w;
     const int oh0 = th * TH, ow0 = tw * TW;
@@ -260,11 +260,11 @@ void conv_wgf(const float* __restrict__ in, int Hin, int Win, const bf16* __rest
             l2[k] = *reinterpret_cast<const bf16x8*>(patch + (a ^ 64));
         };
         rd(0, 0);
-        if constexpr (AA_PIN_WG & 1) __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int i = 0; i < MF; ++i) {
             if (i + 1 < MF) rd(i + 1, (i + 1) & 1);
-            if constexpr (AA_PIN_WG & 2) __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int j = 0; j < NF; ++j) {
                 acc[e][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cur.h[j], h2[i & 1], acc[e][i][j], 0, 0, 0);
@@ -277,7 +277,7 @@ void conv_wgf(const float* __restrict__ in, int Hin, int Win, const bf16* __rest
     // bottom tile of a tall tile) skips its MFMAs: those outputs are discarded
     const bool wave_idle = oh0 + (wm * MF * 16) / NP >= Hout * POOL || (DIAG & 2);
     if (!wave_idle) {
-        if constexpr (AA_WG_PRIO > 0) __builtin_amdgcn_s_setprio(AA_WG_PRIO);
+        __builtin_amdgcn_s_setprio(1);
         for (int kh = 0; kh < KH; ++kh) {
             wg_static_for<0, A>([&](auto ec) {
                 constexpr int e = decltype(ec)::value;
@@ -285,7 +285,7 @@ void conv_wgf(const float* __restrict__ in, int Hin, int Win, const bf16* __rest
                 step(std::integral_constant<int, e % BD>{}, kh * A + e, kh, ec);
             });
         }
-        if constexpr (AA_WG_PRIO > 0) __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_s_setprio(0);
     }
     __syncthreads();  // planes no longer needed: the f32 tile reuses LDS
 

@@ -59,7 +59,7 @@ void conv_wgp(const float* __restrict__ in, int Hin, int Win, const bf16* __rest
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* patch = smem;
 
-    const BlockPos bp = x3_block<true>();
+    const BlockPos bp = x3_block();
     const int n = bp.n, cb = bp.cb;
     const int th = bp.tile / tiles_w, tw = bp.tile - (bp.tile / tiles_w) * tiles_w;
     const int oh0 = th * TH, ow0 = tw * TW;
@@ -158,7 +158,7 @@ void conv_wgp(const float* __restrict__ in, int Hin, int Win, const bf16* __rest
         if (g > 0) __syncthreads();  // every wave is done with the previous planes
         wg_stage<WO, A, 0, NP, PV, NTHR, (DIAG & 1) ? 0 : PV * 8>(patch, oh0, ow0, Hin, Win, g, load4);
         __syncthreads();
-        if constexpr (AA_WG_PRIO > 0) __builtin_amdgcn_s_setprio(AA_WG_PRIO);
+        __builtin_amdgcn_s_setprio(1);
         if constexpr ((DIAG & 2) == 0) {
             if constexpr (WPL % BD == 0) {
                 // the B sets alternate the same way every row: a runtime row loop
@@ -179,7 +179,7 @@ void conv_wgp(const float* __restrict__ in, int Hin, int Win, const bf16* __rest
                 });
             }
         }
-        if constexpr (AA_WG_PRIO > 0) __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_s_setprio(0);
     });
     __syncthreads();  // planes no longer needed
 

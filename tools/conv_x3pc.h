@@ -156,13 +156,13 @@ void conv_x3pc(const float* __restrict__ in, const bf16* __restrict__ wt, const 
                     read_b(0, 0);
 #pragma unroll
                     for (int st = 0; st < AD; ++st) read_a(patch, st);
-                    if (AA_X3_PRIO > 0) __builtin_amdgcn_s_setprio(AA_X3_PRIO);
+                    __builtin_amdgcn_s_setprio(1);
 #pragma unroll
                     for (int st = 0; st < NS; ++st) {
                         const int t = st / MF, i = st % MF, sa = st % (AD + 1), sb = t & 1;
                         if (i == 0 && t + 1 < NTAP) read_b(sb ^ 1, t + 1);
                         if (st + AD < NS) read_a(patch, st + AD);
-                        if constexpr (AA_PIN_X3 & 2) __builtin_amdgcn_sched_barrier(0);
+                        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                         for (int j = 0; j < NF; ++j) {
                             acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh[sb][j], ah[sa], acc[i][j], 0, 0, 0);
@@ -171,7 +171,7 @@ void conv_x3pc(const float* __restrict__ in, const bf16* __restrict__ wt, const 
                         }
                     }
                 }
-                if (AA_X3_PRIO > 0) __builtin_amdgcn_s_setprio(0);
+                __builtin_amdgcn_s_setprio(0);
                 __syncthreads();  // (M) the producers have drained item k - 1 from E
                 float* E = E0;
 #pragma unroll
@@ -197,7 +197,7 @@ void conv_x3pc(const float* __restrict__ in, const bf16* __restrict__ wt, const 
     const int pw = wave - NC, ptid = threadIdx.x - NC * 64;
     uint32_t* const Xs = reinterpret_cast<uint32_t*>(smem + 2 * PC_PATCH + PC_ETILE + PC_BLDS + pw * PC_XBYTES);
     const int l32 = lane & 31, kg = lane >> 5;
-    // first-layer weights and bias (conv_x3's AA_F1_KPACK operand layout)
+    // first-layer weights and bias (conv_x3's fused first layer's operand layout)
     bf16x8 wa{}, wal{};
     f32x16 cbias{};
     {
