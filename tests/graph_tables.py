@@ -227,6 +227,54 @@ def forward3(L, table, prec, x):
     return out
 
 
+GUARD = 256  # floats of NaN before and after the input (a multiple of 64: the kernels load float4s)
+
+
+def guarded_input(x, device="cuda"):
+    """x on the device inside a larger NaN-filled allocation: (the view of x, the
+    allocation).  A kernel that reads outside the batch reads NaN."""
+    import torch
+    buf = torch.full((GUARD + x.size + GUARD,), float("nan"), dtype=torch.float32, device=device)
+    xt = buf[GUARD:GUARD + x.size].view(x.shape)
+    xt.copy_(torch.from_numpy(x))
+    assert xt.is_contiguous() and xt.data_ptr() % 256 == 0
+    return xt, buf
+
+
+def forward3_guarded(L, table, prec, x):
+    """forward3 with traps: the input between NaN guard bands (guarded_input), the
+    workspace filled with NaN bytes before each of the three calls (an element no
+    block writes, or a split-K slice nobody wrote, stays NaN), logits and probs
+    NaN-filled too.  Returns ([logits] * 3, [probs] * 3, sigmoid_out)."""
+    import torch
+    nodes, blob, (H, W, Cin) = table
+    h = C.c_void_p()
+    _lib.check(L.aa_graph_create(nodes, len(nodes), blob.ctypes.data, blob.size, H, W, Cin, PRECS[prec], C.byref(h)),
+               "aa_graph_create")
+    lay = _lib.GraphLayout()
+    assert L.aa_graph_plan_layout(h, C.byref(lay)) == 0
+    n, nl = x.shape[0], L.aa_graph_n_outputs(h)
+    logits, probs = [], []
+    s = torch.cuda.Stream()
+    with torch.cuda.stream(s):
+        xt, keep = guarded_input(x)
+        ws = torch.empty(L.aa_graph_workspace_bytes(h, n), dtype=torch.uint8, device=xt.device)
+        lg = torch.empty((n, nl), dtype=torch.float32, device=xt.device)
+        pr = torch.empty((n, nl), dtype=torch.float32, device=xt.device)
+        for _ in range(3):
+            ws.fill_(0xFF)
+            lg.fill_(float("nan"))
+            pr.fill_(float("nan"))
+            _lib.check(L.aa_graph_forward(h, _lib.dptr(xt), n, _lib.dptr(lg), _lib.dptr(pr), _lib.dptr(ws), ws.numel(),
+                                          _lib.stream_ptr(s)), "aa_graph_forward")
+            logits.append(lg.cpu().numpy().copy())
+            probs.append(pr.cpu().numpy().copy())
+    torch.cuda.synchronize()
+    L.aa_graph_destroy(h)
+    del keep
+    return logits, probs, bool(lay.sigmoid_out)
+
+
 def node_digest(node):
     """One node of describe() as the golden file keeps it: [name, launch
     variant, the first 16 hex digits of the SHA-256 over every field (name,
