@@ -124,6 +124,19 @@ class FlacInfo(C.Structure):
                 ("total_frames", C.c_int64)]
 
 
+class FlacFrame(C.Structure):
+    _fields_ = [("offset", C.c_int64), ("out_at", C.c_int64), ("nbytes", C.c_int32), ("block", C.c_int32),
+                ("keep", C.c_int32), ("channels", C.c_int32), ("bits", C.c_int32), ("stream", C.c_int32)]
+
+
+# aa_flac_status (include/aa.h)
+AA_FLAC_OK = 0
+AA_FLAC_CRC = 1
+AA_FLAC_MALFORMED = 2
+AA_FLAC_FALLBACK = 3
+AA_FLAC_WG = 64
+
+
 class VorbisInfo(C.Structure):
     _fields_ = [("sample_rate", C.c_int32), ("channels", C.c_int32), ("blocksize_0", C.c_int32),
                 ("blocksize_1", C.c_int32), ("total_frames", C.c_int64)]
@@ -247,6 +260,13 @@ _SIGS = {
                             C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "aa_flac_info": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(FlacInfo)]),
     "aa_flac_decode": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
+    "aa_flac_index": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(FlacInfo), C.c_void_p, C.c_int64,
+                                C.POINTER(C.c_int64)]),
+    "aa_flac_device_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int64]),
+    "aa_flac_decode_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "aa_flac_decode_frames_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "aa_vorbis_info": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(VorbisInfo)]),
     "aa_vorbis_decode": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
     "aa_read_file": (C.c_int, [C.c_char_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),

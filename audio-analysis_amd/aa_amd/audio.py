@@ -34,12 +34,15 @@ def _to_mono(q, channels):
     return np.ascontiguousarray(x, dtype=np.float32)
 
 
-def _is_flac(data):
-    if data[:3] == b"ID3" and len(data) >= 10:  # ID3v2 tag in front of the stream
-        sz = (data[6] & 0x7F) << 21 | (data[7] & 0x7F) << 14 | (data[8] & 0x7F) << 7 | (data[9] & 0x7F)
-        off = 10 + sz + (10 if data[5] & 0x10 else 0)
-        return data[off:off + 4] == b"fLaC"
-    return data[:4] == b"fLaC"
+def _is_flac(data, size=None):
+    """data: bytes, or any uint8 buffer of which the first `size` bytes are the file"""
+    size = len(data) if size is None else size
+    head = bytes(data[:min(size, 10)])
+    if head[:3] == b"ID3" and len(head) >= 10:  # ID3v2 tag in front of the stream
+        sz = (head[6] & 0x7F) << 21 | (head[7] & 0x7F) << 14 | (head[8] & 0x7F) << 7 | (head[9] & 0x7F)
+        off = 10 + sz + (10 if head[5] & 0x10 else 0)
+        return off + 4 <= size and bytes(data[off:off + 4]) == b"fLaC"
+    return head[:4] == b"fLaC"
 
 
 def decode_flac(data):

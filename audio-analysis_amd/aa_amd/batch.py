@@ -12,7 +12,13 @@ K at a time:
   * decode: worker threads read each PCM16 48 kHz WAV straight into a pinned
     host slot (other formats and rates go through ``load_recording``); the
     batch crosses PCIe as int16 and ``aa_pcm_s16_to_f32`` widens it on the
-    device exactly as the host decode would;
+    device exactly as the host decode would.  With ``flac="gpu"`` a FLAC
+    file stays compressed in its slot too: the worker only indexes its frames
+    (``flac_gpu.index``), the compressed bytes cross PCIe, and one
+    ``aa_flac_decode_device`` per batch decodes them into the same int16
+    staging buffer; a file with a frame the device does not vouch for is
+    redone through ``load_recording``, so its samples or its failure are the
+    host route's;
   * get_end: one ``aa_span_nonzero`` launch over every file's chunk spans,
     one readback;
   * signal_noise: ``aa_sn_run_batch`` -- per file the STFT / medians / mask
@@ -63,9 +69,17 @@ class Decoded:
     sr_in: int = SR
     slot: int = -1
     dev: object = None       # the recording's samples in the batch's device PCM
+    flac: object = None      # flac="gpu": the frame table (flac_gpu.FRAME) of the compressed bytes ...
+    comp_t: object = None    # ... which are this pinned torch uint8 view of the slot
+    n_in: int = 0            # frames at sr_in the table decodes to
+    path: str = ""
 
     def frames(self):
         """Host float32 samples at 48 kHz (only band-pass filtered tracks need them)."""
+        if self.f32 is None and self.flac is not None:  # decoded on the device: the host decode, lazily
+            from .audio import _to_mono, decode_flac
+            q, ch, _ = decode_flac(self.comp_t.numpy().tobytes())
+            self.f32 = _to_mono(q, ch)
         if self.f32 is None:
             from .audio import _to_mono
             self.f32 = _to_mono(np.asarray(self.s16), self.channels)
@@ -134,13 +148,25 @@ class SlotPool:
             self._cv.notify()
 
 
-def decode_into(path, pool: SlotPool):
-    """Decode one file; PCM16 48 kHz WAV lands in a pinned slot untouched.
+def flac_mode(flac=None) -> str:
+    """"host" (aa_flac_decode on a decoder thread) or "gpu" (aa_flac_decode_device
+    per batch); None: AA_FLAC, else "gpu" -- the default by the corpus A/B of
+    DESIGN section 4 (`flac_decode_frames`)."""
+    mode = flac or os.environ.get("AA_FLAC") or "gpu"
+    if mode not in ("host", "gpu"):
+        raise ValueError(f"flac={mode!r}: \"host\" or \"gpu\"")
+    return mode
+
+
+def decode_into(path, pool: SlotPool, flac="host"):  # (BatchAnalyser passes its mode)
+    """Decode one file; PCM16 48 kHz WAV lands in a pinned slot untouched, and
+    with flac="gpu" an indexable FLAC file stays there compressed.
     The file comes in with one aa_read_file call (stat, open, read, close
     without the interpreter lock: the decoder threads otherwise queued for it
     behind the lanes' Python at every step)."""
     import ctypes as C
     from . import identify_tracks as it
+    from .audio import _is_flac
     i = pool.get()
     got = C.c_int64(0)
     rc = _lib.lib().aa_read_file(os.fsencode(path), pool.t[i].data_ptr(), pool.bytes, C.byref(got))
@@ -156,6 +182,15 @@ def decode_into(path, pool: SlotPool):
                 t = pool.t[i][off:off + nb].view(torch.int16)
                 return Decoded(n=nb // (2 * ch), sr=sr, s16=buf[off:off + nb].view(np.int16), s16_t=t,
                                channels=ch, slot=i)
+            if flac == "gpu" and _is_flac(buf, got.value):
+                from . import flac_gpu
+                from .resample import out_length
+                ix = flac_gpu.index(buf[:got.value])
+                if ix is not None and ix[0].total_frames > 0 and flac_gpu.fits_batch(ix[1]):
+                    info, tab = ix
+                    return Decoded(n=out_length(info.total_frames, info.sample_rate, SR), sr=SR,
+                                   channels=info.channels, sr_in=info.sample_rate, slot=i, flac=tab,
+                                   comp_t=pool.t[i][:got.value], n_in=info.total_frames, path=str(path))
         except Exception:
             pool.put(i)
             raise
@@ -227,6 +262,13 @@ class _Lane:
         self.sn_ws = None
         self.sn_buf = None
         self.ws = {}  # classify_batch workspaces
+        self.flac = {}  # flac="gpu": compressed bytes, decode workspace, per-frame status, f32 before a resample
+
+    def flac_buffer(self, name, n, dtype):
+        t = self.flac.get(name)
+        if t is None or t.numel() < n:
+            t = self.flac[name] = torch.empty(int(n * 1.25) + 1, dtype=dtype, device=self.dev)
+        return t
 
     def buffers(self, n_f32, n_s16):
         if self.pcm.numel() < n_f32:
@@ -260,7 +302,10 @@ class BatchAnalyser:
     batches in flight."""
 
     def __init__(self, bird_models, analyse_tracks=False, device=None, precision=None, batch=16, workers=8,
-                 lanes=2):
+                 lanes=2, flac=None):
+        """flac: "host" decodes FLAC files on the decoder threads (aa_flac_decode),
+        "gpu" on the device per batch (aa_flac_decode_device); None: AA_FLAC, else "gpu"."""
+        self.flac = flac_mode(flac)
         from .identify_tracks import _group_models
         from .pipeline import Classifier
         self.bird_models = bird_models
@@ -278,15 +323,23 @@ class BatchAnalyser:
         """PCM of the batch into one device f32 buffer (recording r at r.off)."""
         total = sum(r.dec.n for r in recs)
         n16 = sum(r.dec.n * r.dec.channels for r in recs if r.dec.s16 is not None)
+        fl = [r for r in recs if r.dec.flac is not None]
+        n16 += sum(r.dec.n_in * r.dec.channels for r in fl)
         pcm, s16 = lane.buffers(total, n16)
+        comp = lane.flac_buffer("bytes", sum(r.dec.comp_t.numel() for r in fl), torch.uint8) if fl else None
         cur = torch.cuda.current_stream(self.dev)
         lane.copy.wait_stream(cur)  # the lane's previous batch is done with both buffers
-        off = o16 = 0
+        off = o16 = oc = 0
         with torch.cuda.stream(lane.copy):
             for r in recs:
                 r.off = off
                 d = r.dec
-                if d.s16 is not None:
+                if d.flac is not None:  # compressed; decoded into s16[o16:] below
+                    comp[oc:oc + d.comp_t.numel()].copy_(d.comp_t, non_blocking=True)
+                    d.oc, d.o16 = oc, o16
+                    oc += d.comp_t.numel()
+                    o16 += d.n_in * d.channels
+                elif d.s16 is not None:
                     s16[o16:o16 + d.s16_t.numel()].copy_(d.s16_t, non_blocking=True)
                     d.o16 = o16
                     o16 += d.s16_t.numel()
@@ -296,24 +349,83 @@ class BatchAnalyser:
         cur.wait_stream(lane.copy)
         L = _lib.lib()
         from .resample import resample_device
-        # every recording mono PCM16: the int16 and f32 offsets coincide, so one
-        # widening launch covers the batch
-        mono16 = all(r.dec.s16 is not None and r.dec.channels == 1 for r in recs)
+        if fl:
+            pcm, total = self._flac_decode(lane, fl, comp, s16, pcm, total, cur)
+        # every recording mono PCM16 (or FLAC decoded to it) at 48 kHz: the int16
+        # and f32 offsets coincide, so one widening launch covers the batch.  (A
+        # file that failed its host redo counts too: it still holds its place in
+        # both buffers, and only as mono 48 kHz are the two places the same.)
+        mono16 = all((r.dec.s16 is not None or (r.dec.flac is not None and r.dec.sr_in == SR)) and
+                     r.dec.channels == 1 for r in recs)
         if mono16 and total:
             _lib.check(L.aa_pcm_s16_to_f32(_lib.dptr(s16), total, 1, _lib.dptr(pcm), _lib.stream_ptr(cur)),
                        "aa_pcm_s16_to_f32")
         for r in recs:
             d = r.dec
             d.dev = pcm[r.off:r.off + d.n]
-            if mono16:
+            if mono16 or r.err is not None:
                 continue
-            if d.s16 is not None and d.n:
+            if d.flac is not None:
+                if d.sr_in == SR:
+                    _lib.check(L.aa_pcm_s16_to_f32(_lib.dptr(s16) + 2 * d.o16, d.n, d.channels,
+                                                   _lib.dptr(pcm) + 4 * r.off, _lib.stream_ptr(cur)),
+                               "aa_pcm_s16_to_f32")
+                else:  # widen at the file's rate, then librosa.resample to 48 kHz as the host route does
+                    tmp = lane.flac_buffer("f32", d.n_in, torch.float32)[:d.n_in]
+                    _lib.check(L.aa_pcm_s16_to_f32(_lib.dptr(s16) + 2 * d.o16, d.n_in, d.channels, _lib.dptr(tmp),
+                                                   _lib.stream_ptr(cur)), "aa_pcm_s16_to_f32")
+                    resample_device(tmp, d.sr_in, SR, out=d.dev)
+            elif d.s16 is not None and d.n:
                 _lib.check(L.aa_pcm_s16_to_f32(_lib.dptr(s16) + 2 * d.o16, d.n, d.channels,
                                                _lib.dptr(pcm) + 4 * r.off, _lib.stream_ptr(cur)),
                            "aa_pcm_s16_to_f32")
             elif d.s16 is None and d.sr_in != SR:  # librosa.resample to 48 kHz (aa_amd.resample)
                 resample_device(torch.from_numpy(d.f32).to(self.dev), d.sr_in, SR, out=d.dev)
         return pcm[:total]
+
+    def _flac_decode(self, lane, fl, comp, s16, pcm, total, cur):
+        """One aa_flac_decode_device over the batch's FLAC files (compressed
+        bytes in comp, samples into s16), then the per-frame statuses: a file
+        with any frame not OK is redone through load_recording, the host route,
+        whose samples -- or whose "Could not load" -- then stand for it.
+        Returns (pcm, total): the host route may decode another number of
+        samples than the index counted (a crafted stream); fewer use the head
+        of the file's place in pcm, more move the file behind the batch."""
+        from . import flac_gpu
+        from . import identify_tracks as it
+        from .resample import out_length
+        tab = flac_gpu.concat([r.dec.flac for r in fl], [r.dec.oc for r in fl], [r.dec.o16 for r in fl])
+        status = lane.flac_buffer("status", len(tab), torch.int32)[:len(tab)]
+        ws = lane.flac_buffer("ws", max(flac_gpu.workspace_bytes(tab) // 4, 1), torch.int32)
+        flac_gpu.decode_device(comp, flac_gpu.table_to_device(tab, self.dev), len(tab), status, ws, out_s16=s16,
+                               stream=cur)
+        st = status.cpu().numpy()  # before any of these files' samples is used
+        bad = sorted(set(tab["stream"][st != _lib.AA_FLAC_OK].tolist()))
+        redone = []
+        for k in bad:
+            r, d = fl[k], fl[k].dec
+            try:
+                frames, sr = it.load_recording(d.path, resample=None)
+            except Exception as e:
+                logging.error("Could not load %s", d.path, exc_info=True)
+                r.err = e if isinstance(e, ValueError) else Exception(f"Could not load {d.path}")
+                continue
+            d.flac, d.f32, d.sr_in = None, np.ascontiguousarray(frames, dtype=np.float32), int(sr)
+            n = out_length(len(d.f32), d.sr_in, SR)
+            if n > d.n:  # no room in its place: behind the batch
+                r.off = total
+                total += n
+            d.n = n
+            redone.append(r)
+        if total > pcm.numel():
+            grown = torch.empty(int(total * 1.25) + 1, dtype=torch.float32, device=self.dev)
+            grown[:pcm.numel()].copy_(pcm)
+            pcm = lane.pcm = grown
+        for r in redone:
+            d = r.dec
+            if d.sr_in == SR:  # (other rates: the loop in _upload resamples d.f32)
+                pcm[r.off:r.off + d.n].copy_(torch.from_numpy(d.f32), non_blocking=False)
+        return pcm, total
 
     def _get_end(self, pcm, recs):
         """get_end (src/identify_tracks.py:387-413) of every recording, one launch."""
@@ -443,19 +555,23 @@ class BatchAnalyser:
     def process(self, items, lane, pool=None):
         """items: [(file_idx, path, Decoded | Exception, sidecar meta)] -> {file_idx: document}."""
         t0 = time.time()
-        recs, failed = [], []
+        recs, failed, held = [], [], []
         for idx, path, dec, meta in items:
             if isinstance(dec, BaseException):
                 failed.append(_Rec(idx, str(path), None, meta, err=dec))
             else:
                 recs.append(_Rec(idx, str(path), dec, meta))
         if recs:
+            held = recs
             try:
                 with torch.cuda.stream(lane.stream):
                     tm = self.timing
                     t = time.perf_counter()
                     pcm = self._upload(lane, recs)
                     t = tm.lap("upload", t)
+                    held = recs  # (their slots are returned below)
+                    failed += [r for r in recs if r.err is not None]  # a FLAC file the host route could not load
+                    recs = [r for r in recs if r.err is None]
                     self._get_end(pcm, recs)
                     t = tm.lap("get_end", t)
                     self._signal_noise(lane, pcm, recs)
@@ -466,7 +582,7 @@ class BatchAnalyser:
                 # (the slots stay held until here: band-pass filtered tracks
                 # read a recording's host samples during classify)
                 if pool is not None:
-                    for r in recs:
+                    for r in held:
                         if r.dec.slot >= 0:
                             pool.put(r.dec.slot)
                             r.dec.slot = -1
@@ -499,7 +615,7 @@ class BatchAnalyser:
             meta = None
             try:
                 meta = read_sidecar(path)
-                return idx, path, decode_into(path, pool), meta
+                return idx, path, decode_into(path, pool, self.flac), meta
             except Exception as e:
                 logging.error("Could not load %s", path, exc_info=True)
                 return idx, path, Exception(f"Could not load {path}") if not isinstance(e, ValueError) else e, meta

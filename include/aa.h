@@ -576,6 +576,68 @@ int aa_flac_info(const uint8_t* data, size_t len, aa_flac_stream_info* info);
  * stream holds more than cap_frames. */
 int aa_flac_decode(const uint8_t* data, size_t len, int32_t* out, int64_t cap_frames, int64_t* n_frames);
 
+/* FLAC decode on the device (aa_amd/flac_gpu.py, the corpus path): the host
+ * indexes a stream's frames, the compressed bytes cross PCIe, and one call
+ * decodes every frame of every stream of a batch.  The decoder core
+ * (csrc/aa_flac_core.h) is separate code from aa_flac_decode, held to it
+ * sample for sample (tests/test_flac_core.py, tests/test_gpu_flac.py). */
+typedef enum aa_flac_status {
+    AA_FLAC_OK = 0,
+    AA_FLAC_CRC = 1,        /* decode did not end 2 bytes before the frame's end, or CRC-16 mismatch */
+    AA_FLAC_MALFORMED = 2,  /* a header or subframe the host decoder rejects too, or a bad table entry */
+    AA_FLAC_FALLBACK = 3,   /* valid perhaps, but beyond this path's int32 arithmetic: decode on the host */
+} aa_flac_status;
+
+/* One frame of a stream.  40 bytes; host array out of aa_flac_index,
+ * device-resident array for aa_flac_decode_device.  A batch concatenates the
+ * streams' bytes and tables: the caller adds each stream's base to `offset`
+ * and `out_at` and sets `stream`. */
+typedef struct aa_flac_frame {
+    int64_t offset;    /* byte offset of the frame's sync code */
+    int64_t out_at;    /* first output frame, as an element index: frame index * channels */
+    int32_t nbytes;    /* bytes to the next frame start (or the stream's end), CRC-16 included */
+    int32_t block;     /* samples per channel coded in the frame */
+    int32_t keep;      /* samples per channel written: block, less in a last block cut by the total */
+    int32_t channels;  /* 1..8 */
+    int32_t bits;      /* 4..32 */
+    int32_t stream;    /* index of the frame's stream in the batch */
+} aa_flac_frame;
+
+/* Index the frames of a FLAC stream in HOST memory (no HIP call): metadata as
+ * aa_flac_info (and its errors), then every frame start: sync code, reserved
+ * header fields, header CRC-8, the coded number the expected one (frame k for
+ * fixed, the running sample number for variable block size), and the CRC-16
+ * of the bytes since the previous start, so a sync pattern inside a frame's
+ * payload is not taken for a start.  An ID3v1 tag ("TAG", 128 bytes) at the
+ * end is not part of the last frame.  frames NULL: size query (*n_frames);
+ * cap < *n_frames: AA_ERR_WORKSPACE, *n_frames set.  AA_ERR_UNSUPPORTED
+ * (reason in aa_last_error) whenever the table would be less than certain --
+ * a first frame not numbered 0, a header at odds with STREAMINFO, bytes
+ * between frames that are no frame, fewer samples than STREAMINFO states, a
+ * frame above 16 MiB: aa_flac_decode then gives today's samples or error. */
+int aa_flac_index(const uint8_t* data, size_t len, aa_flac_stream_info* info, aa_flac_frame* frames, int64_t cap,
+                  int64_t* n_frames);
+/* AA_FLAC_WG frames share a workgroup (and its workspace slice). */
+#define AA_FLAC_WG 64
+/* Workspace of one aa_flac_decode_device / _host over these (host) frames. */
+size_t aa_flac_device_workspace_bytes(const aa_flac_frame* frames_host, int64_t n_frames);
+/* Decode n_frames frames of bytes[0, n_bytes): frame f writes its `keep`
+ * interleaved samples at out_i32 + out_at (the stream's own integers, as
+ * aa_flac_decode) and / or out_s16 + out_at (ffmpeg's s16: x << (16 - bits)
+ * or x >> (bits - 16)); either may be NULL.  status[f] is an aa_flac_status;
+ * samples of a frame whose status is not AA_FLAC_OK are undefined (inside its
+ * own range).  Every load is inside bytes, every store inside the frame's
+ * output range and workspace slice.  Allocates nothing; n_frames == 0 is
+ * AA_OK; a short workspace AA_ERR_WORKSPACE. */
+int aa_flac_decode_device(const uint8_t* bytes_dev, int64_t n_bytes, const aa_flac_frame* frames_dev,
+                          int64_t n_frames, int32_t* out_i32, int16_t* out_s16, int32_t* status_dev, void* workspace,
+                          size_t workspace_bytes, void* stream);
+/* The same through the same core as a host loop, every pointer HOST memory
+ * (the core's CPU tests; stream is ignored). */
+int aa_flac_decode_frames_host(const uint8_t* bytes, int64_t n_bytes, const aa_flac_frame* frames, int64_t n_frames,
+                               int32_t* out_i32, int16_t* out_s16, int32_t* status, void* workspace,
+                               size_t workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------- Ogg Vorbis decode */
 /* load_recording (src/identify_tracks.py:49-62) decodes through ffmpeg; these
  * decode an Ogg Vorbis stream (RFC 3533 pages, Vorbis I codec: floor 0/1,
