@@ -14,7 +14,7 @@ INCLUDE = PKG.parent.parent / "include"
 LIB = PKG / "libaa.so"
 SOURCES = ["aa_api.cpp", "aa_frontend.hip", "aa_cnn.hip", "aa_scan.hip", "aa_signal.hip", "aa_flac.cpp",
            "aa_vorbis.cpp", "aa_tracks.cpp", "aa_resample.hip", "aa_graph.hip", "aa_sosfilt.hip",
-           "aa_cacophony.hip", "aa_flac_gpu.hip"]
+           "aa_cacophony.hip", "aa_flac_gpu.hip", "aa_vorbis_gpu.hip"]
 ARCH = os.environ.get("AA_OFFLOAD_ARCH", "gfx950")
 # per-source flags: the FFT front end is written in scalar f32; SLP packing it
 # into v_pk_* ops needs paired SGPR constants and register shuffles that push
@@ -36,7 +36,13 @@ EXTRA_FLAGS = {"aa_frontend.hip": ["-fno-slp-vectorize"], "aa_signal.hip": ["-fn
                # scipy's sosfilt arithmetic, operation by operation: the kernels
                # name every rounding (__dmul_rn / __dadd_rn); this keeps the
                # host's one-step matrix (aa_sosfilt_plan) uncontracted too
-               "aa_sosfilt.hip": ["-ffp-contract=off"]}
+               "aa_sosfilt.hip": ["-ffp-contract=off"],
+               # the device Vorbis decoder is held to the host decoder's bits
+               # (aa_vorbis.cpp, built for a host without FMA): a contracted
+               # a * b + c rounds once where the host rounds twice -- in the
+               # float residue / floor / window products and sums, and in the
+               # float64 IMDCT butterflies
+               "aa_vorbis_gpu.hip": ["-ffp-contract=off"]}
 # aa_cacophony.hip takes the default flags: the old cacophony index's window
 # product names its rounding (__dmul_rn), the f64 butterflies and the band
 # sums may contract into FMAs -- its gate is a bound on the band energies'

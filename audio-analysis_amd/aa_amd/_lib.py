@@ -142,6 +142,30 @@ class VorbisInfo(C.Structure):
                 ("blocksize_1", C.c_int32), ("total_frames", C.c_int64)]
 
 
+class VorbisPacket(C.Structure):
+    _fields_ = [("offset", C.c_int64), ("pos", C.c_int64), ("blk_at", C.c_int64), ("nbytes", C.c_int32),
+                ("n", C.c_int32), ("blockflag", C.c_int32), ("prev", C.c_int32), ("next", C.c_int32),
+                ("lstart", C.c_int32), ("rend", C.c_int32), ("stream", C.c_int32)]
+
+
+class VorbisStream(C.Structure):
+    _fields_ = [("setup_at", C.c_int64), ("out_at", C.c_int64), ("frames", C.c_int64), ("s0", C.c_int64),
+                ("first_packet", C.c_int64), ("n_packets", C.c_int64), ("channels", C.c_int32),
+                ("sample_rate", C.c_int32), ("blocksize_0", C.c_int32), ("blocksize_1", C.c_int32),
+                ("ws_need", C.c_int32 * 2)]
+
+
+class VorbisPlan(C.Structure):
+    _fields_ = [("stride", C.c_int64), ("blk_floats", C.c_int64), ("max_out", C.c_int64),
+                ("max_channels", C.c_int32), ("reserved", C.c_int32)]
+
+
+# aa_vorbis_status (include/aa.h)
+AA_VORBIS_OK = 0
+AA_VORBIS_FALLBACK = 1
+AA_VORBIS_WG = 64
+
+
 # the band-pass filter's geometry (include/aa.h AA_SOS_*)
 AA_SOS_MAX_SECTIONS = 2
 AA_SOS_CHUNK = 32
@@ -269,6 +293,18 @@ _SIGS = {
                                              C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "aa_vorbis_info": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(VorbisInfo)]),
     "aa_vorbis_decode": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
+    "aa_vorbis_index": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(VorbisStream), C.c_void_p, C.c_int64,
+                                  C.POINTER(C.c_int64), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                  C.POINTER(C.c_int64)]),
+    "aa_vorbis_device_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                                      C.POINTER(VorbisPlan)]),
+    "aa_vorbis_decode_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                          C.c_void_p, C.c_int64, C.POINTER(VorbisPlan), C.c_void_p, C.c_void_p,
+                                          C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "aa_vorbis_decode_packets_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                                C.c_void_p, C.c_int64, C.POINTER(VorbisPlan), C.c_void_p,
+                                                C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                C.c_void_p]),
     "aa_read_file": (C.c_int, [C.c_char_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
     "aa_tracks_from_signals": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_int32, C.c_void_p,
                                          C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),

@@ -18,7 +18,10 @@ K at a time:
     ``aa_flac_decode_device`` per batch decodes them into the same int16
     staging buffer; a file with a frame the device does not vouch for is
     redone through ``load_recording``, so its samples or its failure are the
-    host route's;
+    host route's.  With ``vorbis="gpu"`` an Ogg Vorbis file goes the same way:
+    the worker indexes it (``vorbis_gpu.index``: packets, block timeline,
+    flattened setup), the packet bytes cross PCIe, and one
+    ``aa_vorbis_decode_device`` per batch decodes them into the staging buffer;
   * get_end: one ``aa_span_nonzero`` launch over every file's chunk spans,
     one readback;
   * signal_noise: ``aa_sn_run_batch`` -- per file the STFT / medians / mask
@@ -71,6 +74,7 @@ class Decoded:
     dev: object = None       # the recording's samples in the batch's device PCM
     flac: object = None      # flac="gpu": the frame table (flac_gpu.FRAME) of the compressed bytes ...
     comp_t: object = None    # ... which are this pinned torch uint8 view of the slot
+    vorbis: object = None    # vorbis="gpu": the index (vorbis_gpu.Indexed); comp_t: its packet bytes in the slot
     n_in: int = 0            # frames at sr_in the table decodes to
     path: str = ""
 
@@ -80,6 +84,9 @@ class Decoded:
             from .audio import _to_mono, decode_flac
             q, ch, _ = decode_flac(self.comp_t.numpy().tobytes())
             self.f32 = _to_mono(q, ch)
+        if self.f32 is None and self.vorbis is not None:  # (the slot holds packets, not the file: read it again)
+            from .audio import decode
+            self.f32 = decode(self.path)[0]
         if self.f32 is None:
             from .audio import _to_mono
             self.f32 = _to_mono(np.asarray(self.s16), self.channels)
@@ -158,9 +165,21 @@ def flac_mode(flac=None) -> str:
     return mode
 
 
-def decode_into(path, pool: SlotPool, flac="host"):  # (BatchAnalyser passes its mode)
+def vorbis_mode(vorbis=None) -> str:
+    """"host" (aa_vorbis_decode on a decoder thread) or "gpu"
+    (aa_vorbis_decode_device per batch); None: AA_VORBIS, else "host" -- opt-in
+    until the corpus A/B of DESIGN section 4 (`vorbis_unpack`) says otherwise."""
+    mode = vorbis or os.environ.get("AA_VORBIS") or "host"
+    if mode not in ("host", "gpu"):
+        raise ValueError(f"vorbis={mode!r}: \"host\" or \"gpu\"")
+    return mode
+
+
+def decode_into(path, pool: SlotPool, flac="host", vorbis="host"):  # (BatchAnalyser passes its modes)
     """Decode one file; PCM16 48 kHz WAV lands in a pinned slot untouched, and
-    with flac="gpu" an indexable FLAC file stays there compressed.
+    with flac="gpu" an indexable FLAC file stays there compressed; with
+    vorbis="gpu" an indexable Ogg Vorbis file stays there as its audio packets
+    (the index writes them over the file's bytes).
     The file comes in with one aa_read_file call (stat, open, read, close
     without the interpreter lock: the decoder threads otherwise queued for it
     behind the lanes' Python at every step)."""
@@ -191,6 +210,15 @@ def decode_into(path, pool: SlotPool, flac="host"):  # (BatchAnalyser passes its
                     return Decoded(n=out_length(info.total_frames, info.sample_rate, SR), sr=SR,
                                    channels=info.channels, sr_in=info.sample_rate, slot=i, flac=tab,
                                    comp_t=pool.t[i][:got.value], n_in=info.total_frames, path=str(path))
+            if vorbis == "gpu" and got.value >= 4 and bytes(buf[:4]) == b"OggS":
+                from . import vorbis_gpu
+                from .resample import out_length
+                ix = vorbis_gpu.index(buf[:got.value], payload=buf)
+                if ix is not None and int(ix.stream["frames"][0]) > 0 and vorbis_gpu.fits_batch(ix):
+                    st = ix.stream[0]
+                    n_in, sr_in = int(st["frames"]), int(st["sample_rate"])
+                    return Decoded(n=out_length(n_in, sr_in, SR), sr=SR, channels=int(st["channels"]), sr_in=sr_in,
+                                   slot=i, vorbis=ix, comp_t=pool.t[i][:ix.payload.size], n_in=n_in, path=str(path))
         except Exception:
             pool.put(i)
             raise
@@ -262,7 +290,8 @@ class _Lane:
         self.sn_ws = None
         self.sn_buf = None
         self.ws = {}  # classify_batch workspaces
-        self.flac = {}  # flac="gpu": compressed bytes, decode workspace, per-frame status, f32 before a resample
+        # flac="gpu" / vorbis="gpu": compressed bytes, decode workspace, per-frame status, f32 before a resample
+        self.flac = {}
 
     def flac_buffer(self, name, n, dtype):
         t = self.flac.get(name)
@@ -279,6 +308,7 @@ class _Lane:
 
 
 SN_CAP = 4096   # components per recording kept in the batch slots
+VORBIS_WS_BYTES = 1 << 30  # workspace one aa_vorbis_decode_device call of a batch may take
 PREFETCH = 2    # batches decoded ahead of the newest batch a lane has taken
 _SN_LOCK = __import__("threading").Lock()
 SN_HEAD = 64    # component rows read back with the counts (more: a second copy)
@@ -302,10 +332,13 @@ class BatchAnalyser:
     batches in flight."""
 
     def __init__(self, bird_models, analyse_tracks=False, device=None, precision=None, batch=16, workers=8,
-                 lanes=2, flac=None):
+                 lanes=2, flac=None, vorbis=None):
         """flac: "host" decodes FLAC files on the decoder threads (aa_flac_decode),
-        "gpu" on the device per batch (aa_flac_decode_device); None: AA_FLAC, else "gpu"."""
+        "gpu" on the device per batch (aa_flac_decode_device); None: AA_FLAC, else "gpu".
+        vorbis: the same for Ogg Vorbis files (aa_vorbis_decode / aa_vorbis_decode_device);
+        None: AA_VORBIS, else "host"."""
         self.flac = flac_mode(flac)
+        self.vorbis = vorbis_mode(vorbis)
         from .identify_tracks import _group_models
         from .pipeline import Classifier
         self.bird_models = bird_models
@@ -324,9 +357,10 @@ class BatchAnalyser:
         total = sum(r.dec.n for r in recs)
         n16 = sum(r.dec.n * r.dec.channels for r in recs if r.dec.s16 is not None)
         fl = [r for r in recs if r.dec.flac is not None]
-        n16 += sum(r.dec.n_in * r.dec.channels for r in fl)
+        vb = [r for r in recs if r.dec.vorbis is not None]
+        n16 += sum(r.dec.n_in * r.dec.channels for r in fl + vb)
         pcm, s16 = lane.buffers(total, n16)
-        comp = lane.flac_buffer("bytes", sum(r.dec.comp_t.numel() for r in fl), torch.uint8) if fl else None
+        comp = lane.flac_buffer("bytes", sum(r.dec.comp_t.numel() for r in fl + vb), torch.uint8) if fl or vb else None
         cur = torch.cuda.current_stream(self.dev)
         lane.copy.wait_stream(cur)  # the lane's previous batch is done with both buffers
         off = o16 = oc = 0
@@ -334,7 +368,7 @@ class BatchAnalyser:
             for r in recs:
                 r.off = off
                 d = r.dec
-                if d.flac is not None:  # compressed; decoded into s16[o16:] below
+                if d.flac is not None or d.vorbis is not None:  # compressed; decoded into s16[o16:] below
                     comp[oc:oc + d.comp_t.numel()].copy_(d.comp_t, non_blocking=True)
                     d.oc, d.o16 = oc, o16
                     oc += d.comp_t.numel()
@@ -351,11 +385,14 @@ class BatchAnalyser:
         from .resample import resample_device
         if fl:
             pcm, total = self._flac_decode(lane, fl, comp, s16, pcm, total, cur)
+        if vb:
+            pcm, total = self._vorbis_decode(lane, vb, comp, s16, pcm, total, cur)
         # every recording mono PCM16 (or FLAC decoded to it) at 48 kHz: the int16
         # and f32 offsets coincide, so one widening launch covers the batch.  (A
         # file that failed its host redo counts too: it still holds its place in
         # both buffers, and only as mono 48 kHz are the two places the same.)
-        mono16 = all((r.dec.s16 is not None or (r.dec.flac is not None and r.dec.sr_in == SR)) and
+        mono16 = all((r.dec.s16 is not None or
+                      ((r.dec.flac is not None or r.dec.vorbis is not None) and r.dec.sr_in == SR)) and
                      r.dec.channels == 1 for r in recs)
         if mono16 and total:
             _lib.check(L.aa_pcm_s16_to_f32(_lib.dptr(s16), total, 1, _lib.dptr(pcm), _lib.stream_ptr(cur)),
@@ -365,7 +402,7 @@ class BatchAnalyser:
             d.dev = pcm[r.off:r.off + d.n]
             if mono16 or r.err is not None:
                 continue
-            if d.flac is not None:
+            if d.flac is not None or d.vorbis is not None:
                 if d.sr_in == SR:
                     _lib.check(L.aa_pcm_s16_to_f32(_lib.dptr(s16) + 2 * d.o16, d.n, d.channels,
                                                    _lib.dptr(pcm) + 4 * r.off, _lib.stream_ptr(cur)),
@@ -392,8 +429,6 @@ class BatchAnalyser:
         samples than the index counted (a crafted stream); fewer use the head
         of the file's place in pcm, more move the file behind the batch."""
         from . import flac_gpu
-        from . import identify_tracks as it
-        from .resample import out_length
         tab = flac_gpu.concat([r.dec.flac for r in fl], [r.dec.oc for r in fl], [r.dec.o16 for r in fl])
         status = lane.flac_buffer("status", len(tab), torch.int32)[:len(tab)]
         ws = lane.flac_buffer("ws", max(flac_gpu.workspace_bytes(tab) // 4, 1), torch.int32)
@@ -401,16 +436,55 @@ class BatchAnalyser:
                                stream=cur)
         st = status.cpu().numpy()  # before any of these files' samples is used
         bad = sorted(set(tab["stream"][st != _lib.AA_FLAC_OK].tolist()))
+        return self._redo_on_host(lane, [fl[k] for k in bad], pcm, total)
+
+    def _vorbis_decode(self, lane, vb, comp, s16, pcm, total, cur):
+        """aa_vorbis_decode_device over the batch's Ogg Vorbis files (packet
+        bytes in comp, samples into s16), then the per-packet statuses, read
+        before any sample is used: a file with any packet not OK is redone
+        through load_recording like a FLAC file (_flac_decode).  The files are
+        taken in as many calls as keep one call's workspace under
+        VORBIS_WS_BYTES (a file alone may exceed it)."""
+        from . import vorbis_gpu as vg
+        groups, size = [[]], 0
+        for r in vb:
+            need = vg.workspace_bytes(r.dec.vorbis.packets, r.dec.vorbis.stream)
+            if groups[-1] and size + need > VORBIS_WS_BYTES:
+                groups.append([])
+                size = 0
+            groups[-1].append(r)
+            size += need
+        bad = []
+        for g in groups:
+            b = vg.concat([r.dec.vorbis for r in g], [r.dec.oc for r in g], [r.dec.o16 for r in g])
+            if not len(b.packets):
+                continue
+            pl, nb = vg.plan(b.packets, b.streams)
+            status = lane.flac_buffer("status", len(b.packets), torch.int32)[:len(b.packets)]
+            ws = lane.flac_buffer("vorbis_ws", max(nb // 8, 1), torch.int64)
+            vg.decode_device(comp, vg.to_device(b.packets, self.dev), len(b.packets), vg.to_device(b.streams, self.dev),
+                             len(b.streams), vg.to_device(b.setups, self.dev), pl, status, ws, out_s16=s16,
+                             out_elems=s16.numel(), stream=cur)
+            st = status.cpu().numpy()  # (orders the decode before the next group reuses the workspace, too)
+            bad += [g[k] for k in sorted(set(b.packets["stream"][st != _lib.AA_VORBIS_OK].tolist()))]
+        return self._redo_on_host(lane, bad, pcm, total)
+
+    def _redo_on_host(self, lane, bad, pcm, total):
+        """The files of `bad` (device-decoded, not vouched for) through
+        load_recording; returns (pcm, total) as _flac_decode describes."""
+        from . import identify_tracks as it
+        from .resample import out_length
         redone = []
-        for k in bad:
-            r, d = fl[k], fl[k].dec
+        for r in bad:
+            d = r.dec
             try:
                 frames, sr = it.load_recording(d.path, resample=None)
             except Exception as e:
                 logging.error("Could not load %s", d.path, exc_info=True)
                 r.err = e if isinstance(e, ValueError) else Exception(f"Could not load {d.path}")
                 continue
-            d.flac, d.f32, d.sr_in = None, np.ascontiguousarray(frames, dtype=np.float32), int(sr)
+            d.flac = d.vorbis = None
+            d.f32, d.sr_in = np.ascontiguousarray(frames, dtype=np.float32), int(sr)
             n = out_length(len(d.f32), d.sr_in, SR)
             if n > d.n:  # no room in its place: behind the batch
                 r.off = total
@@ -615,7 +689,7 @@ class BatchAnalyser:
             meta = None
             try:
                 meta = read_sidecar(path)
-                return idx, path, decode_into(path, pool, self.flac), meta
+                return idx, path, decode_into(path, pool, self.flac, self.vorbis), meta
             except Exception as e:
                 logging.error("Could not load %s", path, exc_info=True)
                 return idx, path, Exception(f"Could not load {path}") if not isinstance(e, ValueError) else e, meta

@@ -92,19 +92,20 @@ def raise_hw_queues(n: int = 16):
 
 
 def run(files, bird_models, analyse_tracks=False, examine_fn=None, rank=0, world=1, device=None, batch=16,
-        flac=None):
+        flac=None, vorbis=None):
     """Classify this rank's share of ``files``; returns {file_idx: summary}
     of ALL files on every rank (after the gather).  ``summary`` is what
     analyse.examine returns plus ``processing_time_seconds`` (src/analyse.py:451-453).
     With a GPU and the real examine, files go ``batch`` at a time through
     aa_amd.batch (the same documents, byte for byte); ``batch=0`` or a
     custom ``examine_fn`` runs them one by one.  ``flac``: where the batched
-    path decodes FLAC files, "host" or "gpu" (batch.flac_mode; None: AA_FLAC)."""
+    path decodes FLAC files, "host" or "gpu" (batch.flac_mode; None: AA_FLAC);
+    ``vorbis``: the same for Ogg Vorbis files (batch.vorbis_mode; None: AA_VORBIS)."""
     mine = shard.shard(list(files), rank, world)
     if examine_fn is None and batch and torch.cuda.is_available():
         from .batch import BatchAnalyser
         ba = BatchAnalyser(bird_models, analyse_tracks, device=torch.device("cuda", torch.cuda.current_device()),
-                           batch=batch, lanes=default_lanes(), flac=flac)
+                           batch=batch, lanes=default_lanes(), flac=flac, vorbis=vorbis)
         return gather_documents(ba.run([(i, str(f)) for i, f in mine]), device=device)
     if examine_fn is None:
         from .analyse import examine as examine_fn

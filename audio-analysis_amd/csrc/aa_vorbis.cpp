@@ -35,7 +35,14 @@
 #include <cstring>
 #include <vector>
 
+#if defined(AA_VORBIS_STANDALONE)
+// tools/vorbis_core_check.cpp includes this file into a plain C++ program (no
+// HIP headers) and supplies aa::set_error and AA_CHECK itself
+#include "../../include/aa.h"
+#else
 #include "aa_common.h"
+#endif
+#include "aa_vorbis_core.h"
 
 namespace {
 
@@ -1018,6 +1025,278 @@ int decode_all(const uint8_t* data, size_t len, float* out, int64_t cap, Decoded
     return AA_OK;
 }
 
+// ------------------------------------------------- index for the device path
+// (aa_vorbis_index, include/aa.h): the header parse above, then the timeline
+// of decode_all with each block's size and window flags read from the head of
+// its packet instead of decoded, and the setup flattened for
+// csrc/aa_vorbis_core.h.
+namespace core = aa_vorbis;
+
+struct Blob {
+    std::vector<int32_t> w;
+    int32_t alloc(size_t words, bool even = false) {
+        if (even && (w.size() & 1)) w.push_back(0);
+        const size_t at = w.size();
+        w.resize(at + words, 0);
+        return (int32_t)at;
+    }
+    template <class T>
+    int32_t put(const T* v, size_t count, bool even = false) {
+        const size_t words = (count * sizeof(T) + 3) / 4;
+        const int32_t at = alloc(words, even);
+        if (count) memcpy(&w[at], v, count * sizeof(T));
+        return at;
+    }
+};
+
+// words of classification buffer residue_decode01 may take for a block of n2
+// bins over at most C channels
+int64_t cls_bound(const Decoder& D, int n2) {
+    int64_t most = 0;
+    const int C = D.channels;
+    for (const Residue& r : D.residues) {
+        const int64_t n = r.type == 2 ? (int64_t)n2 * C : n2;
+        const int64_t ntr = std::min<int64_t>(r.end, n) - std::min<int64_t>(r.begin, n);
+        const int64_t W = std::max<int64_t>(ntr, 0) / r.psize + D.books[r.classbook].dims;
+        most = std::max(most, r.type == 2 ? W : W * C);
+    }
+    return most;
+}
+
+int flatten(const Decoder& D, Blob& B, const char*& why) {
+    const size_t HW = sizeof(core::Hdr) / 4;
+    B.alloc(HW);
+    core::Hdr H{};
+    H.magic = core::MAGIC;
+    H.channels = D.channels;
+    H.bs[0] = D.bs[0];
+    H.bs[1] = D.bs[1];
+    H.n_books = (int32_t)D.books.size();
+    H.n_floors = (int32_t)D.floors.size();
+    H.n_res = (int32_t)D.residues.size();
+    H.n_maps = (int32_t)D.maps.size();
+    H.n_modes = (int32_t)D.modes.size();
+    for (int f = 0; f < 2; ++f) {
+        const int64_t cap = cls_bound(D, D.bs[f] / 2);
+        if (cap + (int64_t)D.channels * D.bs[f] > (1 << 30)) {
+            why = "a residue's classification buffer beyond int32";
+            return AA_ERR_UNSUPPORTED;
+        }
+        H.cls_cap[f] = (int32_t)cap;
+    }
+    std::vector<core::Book> books(D.books.size());
+    H.books = B.alloc(books.size() * sizeof(core::Book) / 4);
+    for (size_t i = 0; i < books.size(); ++i) {
+        const Codebook& cb = D.books[i];
+        core::Book& b = books[i];
+        b.dims = cb.dims;
+        b.entries = cb.entries;
+        b.lookup = cb.lookup;
+        b.single = cb.single;
+        b.single_len = cb.single_len;
+        b.n_nodes = (int32_t)(cb.node.size() / 2);
+        b.node = B.put(cb.node.data(), cb.node.size());
+        b.vq = B.put(cb.vq.data(), cb.vq.size());
+        if (B.w.size() > ((size_t)1 << 28)) {
+            why = "codebook tables beyond 1 GiB";
+            return AA_ERR_UNSUPPORTED;
+        }
+    }
+    memcpy(&B.w[H.books], books.data(), books.size() * sizeof(core::Book));
+    H.floors = B.alloc(D.floors.size() * sizeof(core::Floor1) / 4);
+    for (size_t i = 0; i < D.floors.size(); ++i) {
+        const Floor& f = D.floors[i];
+        core::Floor1 o{};
+        o.type = f.type;
+        o.parts = (int32_t)f.part_class.size();
+        o.mult = f.mult;
+        o.nv = (int32_t)f.X.size();
+        for (size_t k = 0; k < f.part_class.size(); ++k) o.part_class[k] = f.part_class[k];
+        for (size_t c = 0; c < f.cdim.size(); ++c) {
+            o.cdim[c] = f.cdim[c];
+            o.csub[c] = f.csub[c];
+            o.cmaster[c] = f.cmaster[c];
+            for (int j = 0; j < 8; ++j) o.subbooks[c][j] = j < (int)f.subbooks[c].size() ? f.subbooks[c][j] : -1;
+        }
+        for (size_t k = 0; k < f.X.size(); ++k) {
+            o.X[k] = f.X[k];
+            o.order1[k] = f.order1[k];
+            o.lo[k] = f.lo[k];
+            o.hi[k] = f.hi[k];
+        }
+        memcpy(&B.w[H.floors + i * (sizeof(core::Floor1) / 4)], &o, sizeof o);
+    }
+    H.res = B.alloc(D.residues.size() * sizeof(core::Res) / 4);
+    for (size_t i = 0; i < D.residues.size(); ++i) {
+        const Residue& r = D.residues[i];
+        core::Res o{};
+        o.type = r.type;
+        o.begin = r.begin;
+        o.end = r.end;
+        o.psize = r.psize;
+        o.classes = r.classes;
+        o.classbook = r.classbook;
+        for (int c = 0; c < 64; ++c)
+            for (int p = 0; p < 8; ++p) o.books[c][p] = c < r.classes ? r.books[c * 8 + p] : -1;
+        memcpy(&B.w[H.res + i * (sizeof(core::Res) / 4)], &o, sizeof o);
+    }
+    H.maps = B.alloc(D.maps.size() * sizeof(core::Map) / 4);
+    for (size_t i = 0; i < D.maps.size(); ++i) {
+        const Mapping& m = D.maps[i];
+        core::Map o{};
+        o.submaps = m.submaps;
+        o.steps = (int32_t)m.mag.size();
+        for (size_t s = 0; s < m.mag.size(); ++s) {
+            o.mag[s] = m.mag[s];
+            o.ang[s] = m.ang[s];
+        }
+        for (int c = 0; c < D.channels; ++c) o.mux[c] = m.mux[c];
+        for (int s = 0; s < m.submaps; ++s) {
+            o.sub_floor[s] = m.sub_floor[s];
+            o.sub_res[s] = m.sub_res[s];
+        }
+        memcpy(&B.w[H.maps + i * (sizeof(core::Map) / 4)], &o, sizeof o);
+    }
+    std::vector<core::Mode> modes;
+    for (const Mode& md : D.modes) modes.push_back(core::Mode{md.blockflag, md.mapping});
+    H.modes = B.put(modes.data(), modes.size());
+    H.inv_db = B.put(inv_db, 256);
+    for (int f = 0; f < 2; ++f) {
+        const Imdct& I = D.mdct[f];
+        core::Mdct m{};
+        m.Q = I.N / 4;
+        m.pre_c = B.put(I.tw_pre_c.data(), I.tw_pre_c.size(), true);
+        m.pre_s = B.put(I.tw_pre_s.data(), I.tw_pre_s.size(), true);
+        m.post_c = B.put(I.tw_post_c.data(), I.tw_post_c.size(), true);
+        m.post_s = B.put(I.tw_post_s.data(), I.tw_post_s.size(), true);
+        m.fft_c = B.put(I.fft_c.data(), I.fft_c.size(), true);
+        m.fft_s = B.put(I.fft_s.data(), I.fft_s.size(), true);
+        m.rev = B.put(I.rev.data(), I.rev.size());
+        H.mdct[f] = B.put(&m, 1);
+    }
+    // the window variants Decoder::audio can pick: the short block's one, the
+    // long block's four
+    H.win_short = B.put(D.win[0][1][1].data(), D.win[0][1][1].size());
+    for (int pl = 0; pl < 2; ++pl)
+        for (int nl = 0; nl < 2; ++nl) H.win_long[pl * 2 + nl] = B.put(D.win[1][pl][nl].data(), D.win[1][pl][nl].size());
+    if (B.w.size() & 1) B.w.push_back(0);
+    H.words = (int32_t)B.w.size();
+    memcpy(B.w.data(), &H, sizeof H);
+    return AA_OK;
+}
+
+int index_all(const uint8_t* data, size_t len, aa_vorbis_stream* st, uint8_t* payload, int64_t payload_cap,
+              int64_t* payload_bytes, aa_vorbis_packet* packets, int64_t packet_cap, void* setup, int64_t setup_cap,
+              int64_t* setup_bytes) {
+    // the headers exactly as decode_all reads them
+    std::vector<Packet> pk;
+    int64_t last_page = -1;
+    int rc = read_packets(data, len, pk, last_page);
+    if (rc) return rc;
+    AA_CHECK(pk.size() >= 3, AA_ERR_INVALID, "Vorbis: missing headers");
+    Decoder D;
+    rc = D.ident(pk[0]);
+    if (rc) return rc;
+    AA_CHECK(pk[1].data.size() >= 7 && pk[1].data[0] == 3 && memcmp(&pk[1].data[1], "vorbis", 6) == 0,
+             AA_ERR_INVALID, "Vorbis: bad comment header");
+    rc = D.setup(pk[2]);
+    if (rc) return rc;
+    AA_CHECK(D.channels <= core::MAX_CH, AA_ERR_UNSUPPORTED, "aa_vorbis_index: %d channels (the device path takes %d)",
+             D.channels, (int)core::MAX_CH);
+    for (const Floor& f : D.floors)
+        AA_CHECK(f.type == 1, AA_ERR_UNSUPPORTED, "aa_vorbis_index: floor type 0 is decoded on the host");
+    Blob B;
+    const char* why = "";
+    rc = flatten(D, B, why);
+    AA_CHECK(rc == AA_OK, rc, "aa_vorbis_index: %s", why);
+    // the timeline (decode_all): block k starts at p_k, p_0 = bs1
+    struct Blk {
+        size_t i;
+        int64_t p;
+        int n, f, pl, nl, ls, rend;
+    };
+    std::vector<Blk> blks;
+    int64_t p = D.bs[1], prev_n = 0, prev_center = -1, first_center = -1, produced = 0;
+    int64_t start_trim = 0, end_total = -1, bytes = 0;
+    bool first_granule_seen = false;
+    for (size_t i = 3; i < pk.size(); ++i) {
+        int n = 0, f = 0, pl = 1, nl = 1;
+        Bits br(pk[i].data.data(), pk[i].data.size());
+        if (!pk[i].data.empty() && br.get(1) == 0) {  // Decoder::audio's first lines
+            const int mn = (int)br.get(ilog((uint32_t)(D.modes.size() - 1)));
+            if (!br.eop && mn < (int)D.modes.size()) {
+                f = D.modes[mn].blockflag;
+                n = D.bs[f];
+                if (f) {
+                    pl = (int)br.get(1);
+                    nl = (int)br.get(1);
+                }
+            }
+        }
+        if (n > 0) {
+            if (prev_n) p += 3 * prev_n / 4 - n / 4;
+            int ls = 0, rend = n;
+            if (f && !pl) ls = n / 4 - D.bs[0] / 4;
+            if (f && !nl) rend = n * 3 / 4 + D.bs[0] / 4;
+            blks.push_back(Blk{i, p, n, f, pl, nl, ls, rend});
+            bytes += (int64_t)pk[i].data.size();
+            const int64_t center = p + n / 2;
+            if (prev_center < 0) first_center = center;
+            else produced += center - prev_center;
+            prev_center = center;
+            prev_n = n;
+        }
+        if (pk[i].granule >= 0) {
+            const bool last = pk[i].page == last_page;
+            if (!first_granule_seen && !last && pk[i].granule < produced) start_trim = produced - pk[i].granule;
+            first_granule_seen = true;
+            if (last) end_total = pk[i].granule;
+        }
+    }
+    int64_t total = produced - start_trim;
+    if (end_total >= 0) total = std::min(total, end_total);
+    total = std::max<int64_t>(total, 0);
+    const int C = D.channels;
+    memset(st, 0, sizeof *st);
+    st->frames = total;
+    st->s0 = first_center + start_trim;
+    st->n_packets = (int64_t)blks.size();
+    st->channels = C;
+    st->sample_rate = D.rate;
+    st->blocksize_0 = D.bs[0];
+    st->blocksize_1 = D.bs[1];
+    const core::Hdr& H = *reinterpret_cast<const core::Hdr*>(B.w.data());
+    for (int f = 0; f < 2; ++f) st->ws_need[f] = C * D.bs[f] + H.cls_cap[f];
+    *payload_bytes = bytes;
+    *setup_bytes = (int64_t)B.w.size() * 4;
+    AA_CHECK(payload && packets && setup && payload_cap >= bytes && packet_cap >= (int64_t)blks.size() &&
+                 setup_cap >= *setup_bytes,
+             AA_ERR_WORKSPACE, "aa_vorbis_index: %lld payload bytes, %lld packets, %lld setup bytes",
+             (long long)bytes, (long long)blks.size(), (long long)*setup_bytes);
+    memcpy(setup, B.w.data(), (size_t)*setup_bytes);
+    int64_t at = 0, blk_at = 0;
+    for (size_t k = 0; k < blks.size(); ++k) {
+        const Blk& b = blks[k];
+        const std::vector<uint8_t>& d = pk[b.i].data;
+        memcpy(payload + at, d.data(), d.size());
+        aa_vorbis_packet& o = packets[k];
+        o.offset = at;
+        o.pos = b.p;
+        o.blk_at = blk_at;
+        o.nbytes = (int32_t)d.size();
+        o.n = b.n;
+        o.blockflag = b.f;
+        o.prev = b.pl;
+        o.next = b.nl;
+        o.lstart = b.ls;
+        o.rend = b.rend;
+        o.stream = 0;
+        at += (int64_t)d.size();
+        blk_at += (int64_t)b.n * C;
+    }
+    return AA_OK;
+}
+
 }  // namespace
 
 extern "C" int aa_vorbis_info(const uint8_t* data, size_t len, aa_vorbis_stream_info* info) {
@@ -1041,4 +1320,14 @@ extern "C" int aa_vorbis_decode(const uint8_t* data, size_t len, float* out, int
     if (rc) return rc;
     *n_frames = d.total;
     return AA_OK;
+}
+
+extern "C" int aa_vorbis_index(const uint8_t* data, size_t len, aa_vorbis_stream* stream, uint8_t* payload,
+                               int64_t payload_cap, int64_t* payload_bytes, aa_vorbis_packet* packets,
+                               int64_t packet_cap, void* setup, int64_t setup_cap, int64_t* setup_bytes) {
+    AA_CHECK(data && stream && payload_bytes && setup_bytes && payload_cap >= 0 && packet_cap >= 0 && setup_cap >= 0,
+             AA_ERR_INVALID, "aa_vorbis_index: bad argument");
+    static_assert(sizeof(aa_vorbis_packet) == 56 && sizeof(aa_vorbis_stream) == 72, "aa_vorbis_* layout");
+    return index_all(data, len, stream, payload, payload_cap, payload_bytes, packets, packet_cap, setup, setup_cap,
+                     setup_bytes);
 }

@@ -661,6 +661,123 @@ int aa_vorbis_info(const uint8_t* data, size_t len, aa_vorbis_stream_info* info)
  * stream holds more than cap_frames. */
 int aa_vorbis_decode(const uint8_t* data, size_t len, float* out, int64_t cap_frames, int64_t* n_frames);
 
+/* Ogg Vorbis decode on the device (aa_amd/vorbis_gpu.py, the corpus path).
+ * A Vorbis audio packet decodes from its own bits and the setup header alone;
+ * only the overlap-add joins neighbours, and where each block lands in time
+ * follows from the mode bits at the head of each packet.  So the host walks
+ * the pages (CRC-32 verified, as aa_vorbis_decode), reassembles the packets,
+ * lays out the block timeline and flattens the setup header (aa_vorbis_index,
+ * no HIP call); the payload bytes cross PCIe, and one call decodes every
+ * packet of every stream of a batch in three launches: unpack (one lane per
+ * packet: floors, residues, coupling, to spectra), inverse MDCT and window
+ * (one workgroup per packet and channel, float64), overlap-add and the
+ * float -> s16 conversion (one thread per output sample).  The decoder core
+ * (csrc/aa_vorbis_core.h) is separate code from aa_vorbis_decode, held to it
+ * bit for bit (tests/test_vorbis_core.py, tests/test_gpu_vorbis.py). */
+typedef enum aa_vorbis_status {
+    AA_VORBIS_OK = 0,
+    AA_VORBIS_FALLBACK = 1, /* a workspace slice too small, a table entry at odds with the packet's own
+                               bits, or a setup index out of range: decode the file on the host */
+} aa_vorbis_status;
+
+/* One audio packet that produces a block.  56 bytes; host array out of
+ * aa_vorbis_index, device-resident array for aa_vorbis_decode_device.  A batch
+ * concatenates the streams' payloads and tables: the caller adds each
+ * stream's bases to `offset` and `blk_at` and sets `stream`. */
+typedef struct aa_vorbis_packet {
+    int64_t offset;     /* byte offset of the packet in the payload buffer */
+    int64_t pos;        /* timeline index of the block's first sample (the first block of a stream starts at
+                           blocksize_1; block k + 1 starts 3 n_k / 4 - n_k+1 / 4 after block k) */
+    int64_t blk_at;     /* float index of the windowed block in the workspace: channel c at blk_at + c * n */
+    int32_t nbytes;     /* packet size */
+    int32_t n;          /* block size: blocksize_0 or blocksize_1 */
+    int32_t blockflag;  /* 1: a long block */
+    int32_t prev, next; /* long block: the window flags read after the mode number; short block: 1, 1 */
+    int32_t lstart;     /* the window's nonzero span [lstart, rend) inside the block: only it is added */
+    int32_t rend;
+    int32_t stream;     /* index of the packet's stream in the batch */
+} aa_vorbis_packet;
+
+/* A stream of the batch.  72 bytes.  aa_vorbis_index fills it for the stream
+ * alone (setup_at, out_at, first_packet 0); the caller of a batch sets those. */
+typedef struct aa_vorbis_stream {
+    int64_t setup_at;      /* byte offset (a multiple of 8) of the stream's flattened setup in the setup buffer;
+                              streams with byte-identical setups share one */
+    int64_t out_at;        /* first output frame, as an element index into out_s16 / out_f32 */
+    int64_t frames;        /* output frames: exactly aa_vorbis_decode's count (produced - start trim, capped by
+                              the last page's granule), not aa_vorbis_info's estimate */
+    int64_t s0;            /* timeline index of the first output frame */
+    int64_t first_packet;  /* the stream's packets: [first_packet, first_packet + n_packets) of the table */
+    int64_t n_packets;
+    int32_t channels;      /* 1..8 */
+    int32_t sample_rate;
+    int32_t blocksize_0;
+    int32_t blocksize_1;
+    int32_t ws_need[2];    /* floats of unpack workspace a short / a long packet needs */
+} aa_vorbis_stream;
+
+/* Index an Ogg Vorbis stream in HOST memory: headers as aa_vorbis_info (the
+ * same parse, so the same streams are accepted and refused, with the same
+ * codes), then
+ *   payload: the audio packets that produce a block, reassembled from the
+ *            lacing values, back to back (*payload_bytes);
+ *   packets: one record each (stream->n_packets).  A packet Decoder::audio
+ *            skips -- empty, its first bit set, its mode number out of range --
+ *            gets no record and leaves the timeline alone;
+ *   setup:   the flattened setup (*setup_bytes, a multiple of 8; layout in
+ *            csrc/aa_vorbis_core.h): codebook trees and expanded VQ tables,
+ *            floor 1, residue, mapping and mode records, the inverse-dB table,
+ *            per block size the inverse MDCT's twiddle and bit-reversal tables
+ *            as doubles, and the window tables -- all computed here, so the
+ *            device uses the host decoder's own table values.
+ * Any buffer NULL or shorter than needed: AA_ERR_WORKSPACE with the three
+ * sizes set (a size query).  AA_ERR_UNSUPPORTED (reason in aa_last_error) for
+ * what the device path declines: a floor of type 0 in the setup (its curve
+ * needs atan / cos / exp / sqrt in double), more than 8 channels, a workspace
+ * need beyond int32; aa_vorbis_decode then decodes the file. */
+int aa_vorbis_index(const uint8_t* data, size_t len, aa_vorbis_stream* stream, uint8_t* payload, int64_t payload_cap,
+                    int64_t* payload_bytes, aa_vorbis_packet* packets, int64_t packet_cap, void* setup,
+                    int64_t setup_cap, int64_t* setup_bytes);
+/* AA_VORBIS_WG packets share a workgroup of the unpack launch (and its workspace slice). */
+#define AA_VORBIS_WG 64
+/* How one decode call divides its workspace; filled by aa_vorbis_device_workspace_bytes. */
+typedef struct aa_vorbis_plan {
+    int64_t stride;        /* floats of unpack workspace per packet: the largest ws_need of the table */
+    int64_t blk_floats;    /* floats of windowed blocks: the largest blk_at + n * channels */
+    int64_t max_out;       /* the most output elements (frames * channels) of one stream */
+    int32_t max_channels;
+    int32_t reserved;
+} aa_vorbis_plan;
+/* Workspace of one aa_vorbis_decode_device / _packets_host over these (host)
+ * tables: the unpack slices, a used-floor flag per packet and channel, the
+ * windowed blocks.  0 with plan zeroed for an empty or inconsistent table. */
+size_t aa_vorbis_device_workspace_bytes(const aa_vorbis_packet* packets_host, int64_t n_packets,
+                                        const aa_vorbis_stream* streams_host, int64_t n_streams,
+                                        aa_vorbis_plan* plan);
+/* Decode n_packets packets of bytes[0, n_bytes) belonging to n_streams
+ * streams: stream k writes its `frames` interleaved frames at out_s16 + out_at
+ * (ffmpeg's s16: clip(lrint(x * 32768)), NaN -> -32768) and / or out_f32 +
+ * out_at (the decoder's float samples, aa_vorbis_decode's bit for bit); either
+ * may be NULL; out_elems bounds both.  status[p] is an aa_vorbis_status; the
+ * samples of a stream with any packet not AA_VORBIS_OK are undefined (inside
+ * its own range).  Every load is inside bytes / the tables / the setups,
+ * every store inside the stream's output range and the workspace.  plan is
+ * HOST memory.  Allocates nothing; n_packets == 0 or n_streams == 0 is AA_OK
+ * (a stream without packets has no frames); a short workspace
+ * AA_ERR_WORKSPACE. */
+int aa_vorbis_decode_device(const uint8_t* bytes_dev, int64_t n_bytes, const aa_vorbis_packet* packets_dev,
+                            int64_t n_packets, const aa_vorbis_stream* streams_dev, int64_t n_streams,
+                            const void* setups_dev, int64_t setups_bytes, const aa_vorbis_plan* plan,
+                            int16_t* out_s16, float* out_f32, int64_t out_elems, int32_t* status_dev,
+                            void* workspace, size_t workspace_bytes, void* stream);
+/* The same through the same core as host loops, every pointer HOST memory
+ * (the core's CPU tests; stream is ignored). */
+int aa_vorbis_decode_packets_host(const uint8_t* bytes, int64_t n_bytes, const aa_vorbis_packet* packets,
+                                  int64_t n_packets, const aa_vorbis_stream* streams, int64_t n_streams,
+                                  const void* setups, int64_t setups_bytes, const aa_vorbis_plan* plan,
+                                  int16_t* out_s16, float* out_f32, int64_t out_elems, int32_t* status,
+                                  void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- file input of the batched corpus path (aa_amd/batch.py) ----
  * The whole file at path into buf (cap bytes; a pinned staging slot), in one
  * call: open, size, read, close -- the reference reads each file through
