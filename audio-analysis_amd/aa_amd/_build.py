@@ -14,7 +14,7 @@ INCLUDE = PKG.parent.parent / "include"
 LIB = PKG / "libaa.so"
 SOURCES = ["aa_api.cpp", "aa_frontend.hip", "aa_cnn.hip", "aa_scan.hip", "aa_signal.hip", "aa_flac.cpp",
            "aa_vorbis.cpp", "aa_tracks.cpp", "aa_resample.hip", "aa_graph.hip", "aa_sosfilt.hip",
-           "aa_cacophony.hip", "aa_flac_gpu.hip", "aa_vorbis_gpu.hip"]
+           "aa_cacophony.hip", "aa_flac_gpu.hip", "aa_vorbis_gpu.hip", "aa_mp3.cpp", "aa_mp3_gpu.hip"]
 ARCH = os.environ.get("AA_OFFLOAD_ARCH", "gfx950")
 # per-source flags: the FFT front end is written in scalar f32; SLP packing it
 # into v_pk_* ops needs paired SGPR constants and register shuffles that push
@@ -42,7 +42,11 @@ EXTRA_FLAGS = {"aa_frontend.hip": ["-fno-slp-vectorize"], "aa_signal.hip": ["-fn
                # a * b + c rounds once where the host rounds twice -- in the
                # float residue / floor / window products and sums, and in the
                # float64 IMDCT butterflies
-               "aa_vorbis_gpu.hip": ["-ffp-contract=off"]}
+               "aa_vorbis_gpu.hip": ["-ffp-contract=off"],
+               # the MP3 decoder is one core (aa_mp3_core.h) run on the host and on
+               # the device, equal bit for bit: neither side may fuse the float64
+               # multiply-adds of the requantiser, the IMDCT sums or the synthesis
+               "aa_mp3.cpp": ["-ffp-contract=off"], "aa_mp3_gpu.hip": ["-ffp-contract=off"]}
 # aa_cacophony.hip takes the default flags: the old cacophony index's window
 # product names its rounding (__dmul_rn), the f64 butterflies and the band
 # sums may contract into FMAs -- its gate is a bound on the band energies'

@@ -166,6 +166,34 @@ AA_VORBIS_FALLBACK = 1
 AA_VORBIS_WG = 64
 
 
+class Mp3Info(C.Structure):
+    _fields_ = [("sample_rate", C.c_int32), ("channels", C.c_int32), ("total_frames", C.c_int64),
+                ("n_frames", C.c_int32), ("delay", C.c_int32), ("padding", C.c_int32), ("reserved", C.c_int32)]
+
+
+class Mp3Frame(C.Structure):
+    _fields_ = [("main_at", C.c_int64), ("main_lo", C.c_int64), ("main_end", C.c_int64), ("stream", C.c_int32),
+                ("number", C.c_int32), ("ms", C.c_int32), ("nodata", C.c_int32), ("scfsi", C.c_int32 * 2),
+                ("part2_3_length", C.c_int32 * 4), ("big_values", C.c_int32 * 4), ("global_gain", C.c_int32 * 4),
+                ("scalefac_compress", C.c_int32 * 4), ("window_switching", C.c_int32 * 4),
+                ("block_type", C.c_int32 * 4), ("mixed", C.c_int32 * 4), ("table_select", C.c_int32 * 12),
+                ("subblock_gain", C.c_int32 * 12), ("region0_count", C.c_int32 * 4), ("region1_count", C.c_int32 * 4),
+                ("preflag", C.c_int32 * 4), ("scalefac_scale", C.c_int32 * 4), ("count1table_select", C.c_int32 * 4)]
+
+
+class Mp3Stream(C.Structure):
+    _fields_ = [("out_at", C.c_int64), ("frames", C.c_int64), ("skip", C.c_int64), ("first_frame", C.c_int64),
+                ("n_frames", C.c_int64), ("channels", C.c_int32), ("sample_rate", C.c_int32),
+                ("sr_index", C.c_int32), ("reserved", C.c_int32)]
+
+
+# aa_mp3_status (include/aa.h)
+AA_MP3_OK = 0
+AA_MP3_NODATA = 1
+AA_MP3_MALFORMED = 2
+AA_MP3_WG = 64
+
+
 # the band-pass filter's geometry (include/aa.h AA_SOS_*)
 AA_SOS_MAX_SECTIONS = 2
 AA_SOS_CHUNK = 32
@@ -305,6 +333,20 @@ _SIGS = {
                                                 C.c_void_p, C.c_int64, C.POINTER(VorbisPlan), C.c_void_p,
                                                 C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t,
                                                 C.c_void_p]),
+    "aa_mp3_info": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(Mp3Info)]),
+    "aa_mp3_decode": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
+    "aa_mp3_index": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(Mp3Stream), C.c_void_p, C.c_int64,
+                               C.POINTER(C.c_int64), C.c_void_p, C.c_int64]),
+    "aa_mp3_tables": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
+    "aa_mp3_table": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
+    "aa_mp3_synth_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
+    "aa_mp3_device_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "aa_mp3_decode_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                       C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                       C.c_size_t, C.c_void_p]),
+    "aa_mp3_decode_frames_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                            C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                            C.c_size_t]),
     "aa_read_file": (C.c_int, [C.c_char_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
     "aa_tracks_from_signals": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_int32, C.c_void_p,
                                          C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),

@@ -14,8 +14,16 @@ decoder left-justifies a b-bit sample into s16 (b <= 16) or s32, so the s16
 value is ``x << (16 - b)`` or ``x >> (b - 16)``.  Ogg Vorbis streams are
 decoded natively too (``aa_vorbis_decode``, host code): ffmpeg's Vorbis decoder
 outputs float, which libswresample converts to s16 as for float WAV
-(``clip(lrint(x * 32768))``).  Other lossy containers (MP3, AAC/M4A, Opus)
-need a codec this image does not have and are rejected.
+(``clip(lrint(x * 32768))``).  MPEG-1 Layer III (MP3) streams are decoded
+natively as well (``aa_mp3_decode``: one float64 decoder core, csrc/aa_mp3_core.h,
+run on the host here and on the device in the batched corpus path), rounded
+once to float32 and converted to s16 the same way; a LAME-style tag trims the
+encoder delay and padding as ffmpeg's demuxer does.  ffmpeg's own MP3 decoder
+works in float32 with a fast DCT, so its s16 samples may differ from these by
++-1 LSB: parity with ffmpeg's samples is unpinned (none to compare with).  MPEG-2 /
+2.5, Layers I and II, free-format and intensity-stereo streams are declined.
+Other lossy containers (AAC/M4A, Opus) need a codec this image does not have
+and are rejected.
 Resampling to 48 kHz (librosa soxr_hq in the reference) runs on the GPU with
 a filter designed to libsoxr's HQ specification (aa_amd.resample) -- parity
 with libsoxr's samples unpinned: libsoxr is not available.
@@ -97,9 +105,66 @@ def decode_vorbis(data):
     return out[: n.value * info.channels], info.channels, info.sample_rate
 
 
+def _mp3_header(data, pos, size):
+    """(frame length, (version, layer, rate index)) of a valid MPEG audio header
+    with a bitrate at data[pos:pos + 4], else None."""
+    if pos + 4 > size:
+        return None
+    b = bytes(data[pos:pos + 4])
+    if b[0] != 0xFF or (b[1] & 0xE0) != 0xE0:
+        return None
+    version, layer, br, sr = (b[1] >> 3) & 3, (b[1] >> 1) & 3, b[2] >> 4, (b[2] >> 2) & 3
+    if version == 1 or layer != 1 or br in (0, 15) or sr == 3:
+        return None
+    if version != 3:  # MPEG-2 / 2.5 Layer III: recognised (and declined by the decoder)
+        return 0, (version, layer, sr)
+    kbps = (0, 32, 40, 48, 56, 64, 80, 96, 112, 128, 160, 192, 224, 256, 320)[br]
+    return 144000 * kbps // (44100, 48000, 32000)[sr] + ((b[2] >> 1) & 1), (version, layer, sr)
+
+
+def _is_mp3(data, size=None):
+    """An MPEG Layer III stream: behind any ID3v2 tags a valid Layer III header
+    and, at its frame length, a second one of the same version, layer and rate
+    (or the end of the file).  data: bytes or a uint8 buffer."""
+    size = len(data) if size is None else size
+    pos = 0
+    while pos + 10 <= size and bytes(data[pos:pos + 3]) == b"ID3":
+        h = bytes(data[pos:pos + 10])
+        if h[3] == 0xFF or h[4] == 0xFF or (h[6] | h[7] | h[8] | h[9]) & 0x80:
+            break
+        pos += 10 + ((h[6] << 21) | (h[7] << 14) | (h[8] << 7) | h[9]) + (10 if h[5] & 0x10 else 0)
+    first = _mp3_header(data, pos, size)
+    if first is None:
+        return False
+    if first[0] == 0:
+        return True
+    nxt = pos + first[0]
+    if nxt + 4 > size:
+        return nxt <= size
+    second = _mp3_header(data, nxt, size)
+    return second is not None and second[1] == first[1]
+
+
+def decode_mp3(data):
+    """MP3 bytes -> (decoded float32 [frames * channels], channels, sr)."""
+    import ctypes as C
+    from ._lib import Mp3Info, check, lib
+    buf = np.frombuffer(data, np.uint8)
+    info = Mp3Info()
+    check(lib().aa_mp3_info(buf.ctypes.data, buf.size, C.byref(info)), "aa_mp3_info")
+    n = C.c_int64()
+    cap = int(info.total_frames)  # (counted from the frames found: bounded by the file's size)
+    out = np.empty(max(cap, 1) * info.channels, np.float32)
+    check(lib().aa_mp3_decode(buf.ctypes.data, buf.size, out.ctypes.data, cap, C.byref(n)), "aa_mp3_decode")
+    return out[: n.value * info.channels], info.channels, info.sample_rate
+
+
 def decode(path):
     with open(path, "rb") as f:
         data = f.read()
+    if _is_mp3(data):
+        f, channels, sr = decode_mp3(data)
+        return _to_mono(_float_to_s16(f), channels), int(sr)
     if _is_flac(data):
         q, channels, sr = decode_flac(data)
         return _to_mono(q, channels), int(sr)
@@ -107,7 +172,7 @@ def decode(path):
         f, channels, sr = decode_vorbis(data)
         return _to_mono(_float_to_s16(f), channels), int(sr)
     if len(data) < 12 or data[:4] not in (b"RIFF", b"RF64") or data[8:12] != b"WAVE":
-        raise ValueError(f"{path}: not a RIFF/WAVE, FLAC or Ogg Vorbis file")
+        raise ValueError(f"{path}: not a RIFF/WAVE, FLAC, Ogg Vorbis or MP3 file")
     mv = memoryview(data)  # chunk bodies as views: no copy of the sample payload
     pos, fmt, payload = 12, None, None
     while pos + 8 <= len(data):

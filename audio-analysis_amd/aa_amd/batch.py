@@ -21,7 +21,11 @@ K at a time:
     host route's.  With ``vorbis="gpu"`` an Ogg Vorbis file goes the same way:
     the worker indexes it (``vorbis_gpu.index``: packets, block timeline,
     flattened setup), the packet bytes cross PCIe, and one
-    ``aa_vorbis_decode_device`` per batch decodes them into the staging buffer;
+    ``aa_vorbis_decode_device`` per batch decodes them into the staging buffer.
+    With ``mp3="gpu"`` an MP3 file likewise: the worker indexes it
+    (``mp3_gpu.index``: headers, side info, the bit reservoir laid out flat),
+    the main data cross PCIe, and one ``aa_mp3_decode_device`` per batch
+    decodes them -- with the host decoder's own core, so no file is redone;
   * get_end: one ``aa_span_nonzero`` launch over every file's chunk spans,
     one readback;
   * signal_noise: ``aa_sn_run_batch`` -- per file the STFT / medians / mask
@@ -75,6 +79,7 @@ class Decoded:
     flac: object = None      # flac="gpu": the frame table (flac_gpu.FRAME) of the compressed bytes ...
     comp_t: object = None    # ... which are this pinned torch uint8 view of the slot
     vorbis: object = None    # vorbis="gpu": the index (vorbis_gpu.Indexed); comp_t: its packet bytes in the slot
+    mp3: object = None       # mp3="gpu": the index (mp3_gpu.Indexed); comp_t: its flat main data in the slot
     n_in: int = 0            # frames at sr_in the table decodes to
     path: str = ""
 
@@ -84,7 +89,8 @@ class Decoded:
             from .audio import _to_mono, decode_flac
             q, ch, _ = decode_flac(self.comp_t.numpy().tobytes())
             self.f32 = _to_mono(q, ch)
-        if self.f32 is None and self.vorbis is not None:  # (the slot holds packets, not the file: read it again)
+        if self.f32 is None and (self.vorbis is not None or self.mp3 is not None):
+            # (the slot holds packets / main data, not the file: read it again)
             from .audio import decode
             self.f32 = decode(self.path)[0]
         if self.f32 is None:
@@ -175,11 +181,22 @@ def vorbis_mode(vorbis=None) -> str:
     return mode
 
 
-def decode_into(path, pool: SlotPool, flac="host", vorbis="host"):  # (BatchAnalyser passes its modes)
+def mp3_mode(mp3=None) -> str:
+    """"host" (aa_mp3_decode on a decoder thread) or "gpu" (aa_mp3_decode_device
+    per batch); None: AA_MP3, else "host" -- opt-in until a corpus A/B on the
+    device says otherwise (`mp3_unpack`)."""
+    mode = mp3 or os.environ.get("AA_MP3") or "host"
+    if mode not in ("host", "gpu"):
+        raise ValueError(f"mp3={mode!r}: \"host\" or \"gpu\"")
+    return mode
+
+
+def decode_into(path, pool: SlotPool, flac="host", vorbis="host", mp3="host"):  # (BatchAnalyser passes its modes)
     """Decode one file; PCM16 48 kHz WAV lands in a pinned slot untouched, and
     with flac="gpu" an indexable FLAC file stays there compressed; with
     vorbis="gpu" an indexable Ogg Vorbis file stays there as its audio packets
-    (the index writes them over the file's bytes).
+    (the index writes them over the file's bytes), and with mp3="gpu" an MP3
+    file as its flat main data (likewise).
     The file comes in with one aa_read_file call (stat, open, read, close
     without the interpreter lock: the decoder threads otherwise queued for it
     behind the lanes' Python at every step)."""
@@ -219,6 +236,18 @@ def decode_into(path, pool: SlotPool, flac="host", vorbis="host"):  # (BatchAnal
                     n_in, sr_in = int(st["frames"]), int(st["sample_rate"])
                     return Decoded(n=out_length(n_in, sr_in, SR), sr=SR, channels=int(st["channels"]), sr_in=sr_in,
                                    slot=i, vorbis=ix, comp_t=pool.t[i][:ix.payload.size], n_in=n_in, path=str(path))
+            if mp3 == "gpu":
+                from .audio import _is_mp3
+                if _is_mp3(buf, got.value):
+                    from . import mp3_gpu
+                    from .resample import out_length
+                    ix = mp3_gpu.index(buf[:got.value], payload=buf)
+                    if ix is not None and int(ix.stream["frames"][0]) > 0 and mp3_gpu.fits_batch(ix):
+                        st = ix.stream[0]
+                        n_in, sr_in = int(st["frames"]), int(st["sample_rate"])
+                        return Decoded(n=out_length(n_in, sr_in, SR), sr=SR, channels=int(st["channels"]),
+                                       sr_in=sr_in, slot=i, mp3=ix, comp_t=pool.t[i][:ix.payload.size], n_in=n_in,
+                                       path=str(path))
         except Exception:
             pool.put(i)
             raise
@@ -309,6 +338,7 @@ class _Lane:
 
 SN_CAP = 4096   # components per recording kept in the batch slots
 VORBIS_WS_BYTES = 1 << 30  # workspace one aa_vorbis_decode_device call of a batch may take
+MP3_WS_BYTES = 1 << 30     # the same for aa_mp3_decode_device (sixteen 60 s clips need about 0.86 GB)
 PREFETCH = 2    # batches decoded ahead of the newest batch a lane has taken
 _SN_LOCK = __import__("threading").Lock()
 SN_HEAD = 64    # component rows read back with the counts (more: a second copy)
@@ -332,13 +362,15 @@ class BatchAnalyser:
     batches in flight."""
 
     def __init__(self, bird_models, analyse_tracks=False, device=None, precision=None, batch=16, workers=8,
-                 lanes=2, flac=None, vorbis=None):
+                 lanes=2, flac=None, vorbis=None, mp3=None):
         """flac: "host" decodes FLAC files on the decoder threads (aa_flac_decode),
         "gpu" on the device per batch (aa_flac_decode_device); None: AA_FLAC, else "gpu".
         vorbis: the same for Ogg Vorbis files (aa_vorbis_decode / aa_vorbis_decode_device);
-        None: AA_VORBIS, else "host"."""
+        None: AA_VORBIS, else "host".
+        mp3: the same for MP3 files (aa_mp3_decode / aa_mp3_decode_device); None: AA_MP3, else "host"."""
         self.flac = flac_mode(flac)
         self.vorbis = vorbis_mode(vorbis)
+        self.mp3 = mp3_mode(mp3)
         from .identify_tracks import _group_models
         from .pipeline import Classifier
         self.bird_models = bird_models
@@ -358,9 +390,11 @@ class BatchAnalyser:
         n16 = sum(r.dec.n * r.dec.channels for r in recs if r.dec.s16 is not None)
         fl = [r for r in recs if r.dec.flac is not None]
         vb = [r for r in recs if r.dec.vorbis is not None]
-        n16 += sum(r.dec.n_in * r.dec.channels for r in fl + vb)
+        m3 = [r for r in recs if r.dec.mp3 is not None]
+        n16 += sum(r.dec.n_in * r.dec.channels for r in fl + vb + m3)
         pcm, s16 = lane.buffers(total, n16)
-        comp = lane.flac_buffer("bytes", sum(r.dec.comp_t.numel() for r in fl + vb), torch.uint8) if fl or vb else None
+        comp = (lane.flac_buffer("bytes", sum(r.dec.comp_t.numel() for r in fl + vb + m3), torch.uint8)
+                if fl or vb or m3 else None)
         cur = torch.cuda.current_stream(self.dev)
         lane.copy.wait_stream(cur)  # the lane's previous batch is done with both buffers
         off = o16 = oc = 0
@@ -368,7 +402,7 @@ class BatchAnalyser:
             for r in recs:
                 r.off = off
                 d = r.dec
-                if d.flac is not None or d.vorbis is not None:  # compressed; decoded into s16[o16:] below
+                if d.flac is not None or d.vorbis is not None or d.mp3 is not None:  # compressed; decoded into s16[o16:] below
                     comp[oc:oc + d.comp_t.numel()].copy_(d.comp_t, non_blocking=True)
                     d.oc, d.o16 = oc, o16
                     oc += d.comp_t.numel()
@@ -387,12 +421,15 @@ class BatchAnalyser:
             pcm, total = self._flac_decode(lane, fl, comp, s16, pcm, total, cur)
         if vb:
             pcm, total = self._vorbis_decode(lane, vb, comp, s16, pcm, total, cur)
+        if m3:
+            self._mp3_decode(lane, m3, comp, s16, cur)
         # every recording mono PCM16 (or FLAC decoded to it) at 48 kHz: the int16
         # and f32 offsets coincide, so one widening launch covers the batch.  (A
         # file that failed its host redo counts too: it still holds its place in
         # both buffers, and only as mono 48 kHz are the two places the same.)
         mono16 = all((r.dec.s16 is not None or
-                      ((r.dec.flac is not None or r.dec.vorbis is not None) and r.dec.sr_in == SR)) and
+                      ((r.dec.flac is not None or r.dec.vorbis is not None or r.dec.mp3 is not None) and
+                       r.dec.sr_in == SR)) and
                      r.dec.channels == 1 for r in recs)
         if mono16 and total:
             _lib.check(L.aa_pcm_s16_to_f32(_lib.dptr(s16), total, 1, _lib.dptr(pcm), _lib.stream_ptr(cur)),
@@ -402,7 +439,7 @@ class BatchAnalyser:
             d.dev = pcm[r.off:r.off + d.n]
             if mono16 or r.err is not None:
                 continue
-            if d.flac is not None or d.vorbis is not None:
+            if d.flac is not None or d.vorbis is not None or d.mp3 is not None:
                 if d.sr_in == SR:
                     _lib.check(L.aa_pcm_s16_to_f32(_lib.dptr(s16) + 2 * d.o16, d.n, d.channels,
                                                    _lib.dptr(pcm) + 4 * r.off, _lib.stream_ptr(cur)),
@@ -468,6 +505,30 @@ class BatchAnalyser:
             st = status.cpu().numpy()  # (orders the decode before the next group reuses the workspace, too)
             bad += [g[k] for k in sorted(set(b.packets["stream"][st != _lib.AA_VORBIS_OK].tolist()))]
         return self._redo_on_host(lane, bad, pcm, total)
+
+    def _mp3_decode(self, lane, m3, comp, s16, cur):
+        """aa_mp3_decode_device over the batch's MP3 files (flat main data in
+        comp, samples into s16), in as many calls as keep one call's workspace
+        under MP3_WS_BYTES (a file alone may exceed it).  The device runs the
+        host decoder's core, damaged frames included (silence on both sides),
+        so no status is read back and no file is redone."""
+        from . import mp3_gpu as mg
+        groups, size = [[]], 0
+        for r in m3:
+            need = mg.workspace_bytes(len(r.dec.mp3.frames))
+            if groups[-1] and size + need > MP3_WS_BYTES:
+                groups.append([])
+                size = 0
+            groups[-1].append(r)
+            size += need
+        for g in groups:
+            b = mg.concat([r.dec.mp3 for r in g], [r.dec.oc for r in g], [r.dec.o16 for r in g])
+            if not len(b.frames):
+                continue
+            status = lane.flac_buffer("status", 4 * len(b.frames), torch.int32)[:4 * len(b.frames)]
+            ws = lane.flac_buffer("mp3_ws", max(mg.workspace_bytes(len(b.frames)) // 8, 1), torch.int64)
+            mg.decode_device(comp, mg.to_device(b.frames, self.dev), len(b.frames), mg.to_device(b.streams, self.dev),
+                             len(b.streams), status, ws, out_s16=s16, out_elems=s16.numel(), stream=cur)
 
     def _redo_on_host(self, lane, bad, pcm, total):
         """The files of `bad` (device-decoded, not vouched for) through
@@ -689,7 +750,7 @@ class BatchAnalyser:
             meta = None
             try:
                 meta = read_sidecar(path)
-                return idx, path, decode_into(path, pool, self.flac, self.vorbis), meta
+                return idx, path, decode_into(path, pool, self.flac, self.vorbis, self.mp3), meta
             except Exception as e:
                 logging.error("Could not load %s", path, exc_info=True)
                 return idx, path, Exception(f"Could not load {path}") if not isinstance(e, ValueError) else e, meta

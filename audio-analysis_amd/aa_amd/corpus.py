@@ -92,7 +92,7 @@ def raise_hw_queues(n: int = 16):
 
 
 def run(files, bird_models, analyse_tracks=False, examine_fn=None, rank=0, world=1, device=None, batch=16,
-        flac=None, vorbis=None):
+        flac=None, vorbis=None, mp3=None):
     """Classify this rank's share of ``files``; returns {file_idx: summary}
     of ALL files on every rank (after the gather).  ``summary`` is what
     analyse.examine returns plus ``processing_time_seconds`` (src/analyse.py:451-453).
@@ -100,12 +100,13 @@ def run(files, bird_models, analyse_tracks=False, examine_fn=None, rank=0, world
     aa_amd.batch (the same documents, byte for byte); ``batch=0`` or a
     custom ``examine_fn`` runs them one by one.  ``flac``: where the batched
     path decodes FLAC files, "host" or "gpu" (batch.flac_mode; None: AA_FLAC);
-    ``vorbis``: the same for Ogg Vorbis files (batch.vorbis_mode; None: AA_VORBIS)."""
+    ``vorbis``: the same for Ogg Vorbis files (batch.vorbis_mode; None: AA_VORBIS);
+    ``mp3``: the same for MP3 files (batch.mp3_mode; None: AA_MP3)."""
     mine = shard.shard(list(files), rank, world)
     if examine_fn is None and batch and torch.cuda.is_available():
         from .batch import BatchAnalyser
         ba = BatchAnalyser(bird_models, analyse_tracks, device=torch.device("cuda", torch.cuda.current_device()),
-                           batch=batch, lanes=default_lanes(), flac=flac, vorbis=vorbis)
+                           batch=batch, lanes=default_lanes(), flac=flac, vorbis=vorbis, mp3=mp3)
         return gather_documents(ba.run([(i, str(f)) for i, f in mine]), device=device)
     if examine_fn is None:
         from .analyse import examine as examine_fn

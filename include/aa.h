@@ -778,6 +778,143 @@ int aa_vorbis_decode_packets_host(const uint8_t* bytes, int64_t n_bytes, const a
                                   int16_t* out_s16, float* out_f32, int64_t out_elems, int32_t* status,
                                   void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ MP3 decode */
+/* load_recording (src/identify_tracks.py:49-62) decodes through ffmpeg; these
+ * decode an MPEG-1 Layer III stream (32 / 44.1 / 48 kHz; mono, stereo, dual
+ * channel, joint stereo with MS; long, start, short, stop and mixed blocks;
+ * CBR or VBR, padding, the bit reservoir, the CRC word skipped) held in HOST
+ * memory.  An ID3v2 tag in front is skipped; behind the audio the walk resyncs
+ * forward to a header agreeing with the first in version, layer and rate, else
+ * the stream ends.  A Xing / Info / VBRI frame is not audio; a LAME-style tag
+ * in it trims the output as ffmpeg's demuxer does (delay + 529 frames off the
+ * start, everything from n_frames * 1152 - padding + 529 on off the end).
+ * One decoder core (csrc/aa_mp3_core.h), float64 throughout, rounded once to
+ * float32: the host decoder is that core as host loops, the device decoder
+ * the same code in three kernels, equal bit for bit.  Declined with
+ * AA_ERR_UNSUPPORTED: MPEG-2 / 2.5, Layers I and II, free format, a stream
+ * with any intensity-stereo frame. */
+typedef struct aa_mp3_stream_info {
+    int32_t sample_rate;
+    int32_t channels;       /* 1 or 2 */
+    int64_t total_frames;   /* output frames (samples per channel) after the trim */
+    int32_t n_frames;       /* audio frames (1152 samples each) */
+    int32_t delay, padding; /* of the LAME-style tag; -1, -1 without one */
+    int32_t reserved;
+} aa_mp3_stream_info;
+
+typedef enum aa_mp3_status {
+    AA_MP3_OK = 0,
+    AA_MP3_NODATA = 1,    /* the frame's main_data_begin reaches before the stream's data: silence */
+    AA_MP3_MALFORMED = 2, /* the granule's side info cannot be honoured (big values beyond part2_3_length or
+                             576, scalefactors beyond part2_3_length, bits past the reservoir, a table or
+                             block type that does not exist): silence */
+} aa_mp3_status;
+
+/* One audio frame.  336 bytes.  The main data of a stream's frames lie back to
+ * back in the payload (the bit reservoir laid out flat); a batch concatenates
+ * payloads and tables: the caller adds each stream's byte base to main_at,
+ * main_lo and main_end, and sets `stream`. */
+typedef struct aa_mp3_frame {
+    int64_t main_at;  /* payload byte where the frame's granules begin: its own data's start - main_data_begin */
+    int64_t main_lo;  /* first payload byte of the frame's stream */
+    int64_t main_end; /* one past the frame's own main data */
+    int32_t stream;   /* index of the frame's stream in the batch */
+    int32_t number;   /* index of the frame in its stream */
+    int32_t ms;       /* joint stereo with MS on */
+    int32_t nodata;   /* main_at < main_lo */
+    int32_t scfsi[2]; /* per channel, band group 0 in bit 3 */
+    /* the side info of granule gr of channel ch at [gr * 2 + ch] (table_select
+     * and subblock_gain: three values each from [(gr * 2 + ch) * 3]);
+     * block_type is 0 without window switching, and region0_count /
+     * region1_count hold the standard's implied values with it */
+    int32_t part2_3_length[4];
+    int32_t big_values[4];
+    int32_t global_gain[4];
+    int32_t scalefac_compress[4];
+    int32_t window_switching[4];
+    int32_t block_type[4];
+    int32_t mixed[4];
+    int32_t table_select[12];
+    int32_t subblock_gain[12];
+    int32_t region0_count[4];
+    int32_t region1_count[4];
+    int32_t preflag[4];
+    int32_t scalefac_scale[4];
+    int32_t count1table_select[4];
+} aa_mp3_frame;
+
+/* A stream of the batch.  56 bytes.  aa_mp3_index fills it for the stream
+ * alone (out_at, first_frame 0). */
+typedef struct aa_mp3_stream {
+    int64_t out_at;      /* first output frame, as an element index into out_s16 / out_f32 */
+    int64_t frames;      /* output frames after the trim */
+    int64_t skip;        /* decoded frames dropped in front */
+    int64_t first_frame; /* the stream's frames: [first_frame, first_frame + n_frames) of the table */
+    int64_t n_frames;
+    int32_t channels;
+    int32_t sample_rate;
+    int32_t sr_index;    /* 0: 44.1 kHz, 1: 48 kHz, 2: 32 kHz */
+    int32_t reserved;
+} aa_mp3_stream;
+
+int aa_mp3_info(const uint8_t* data, size_t len, aa_mp3_stream_info* info);
+/* out: host float32 [cap_frames][channels], or NULL to count only; n_frames:
+ * frames decoded.  AA_ERR_WORKSPACE when the stream holds more than
+ * cap_frames.  aa_mp3_index plus aa_mp3_decode_frames_host. */
+int aa_mp3_decode(const uint8_t* data, size_t len, float* out, int64_t cap_frames, int64_t* n_frames);
+/* Index a stream in HOST memory: payload takes the frames' main-data bytes
+ * back to back (*payload_bytes; it may be the buffer holding data: every byte
+ * is read before it is overwritten), frames one record per audio frame
+ * (stream->n_frames).  Either buffer NULL or short: AA_ERR_WORKSPACE with
+ * both sizes set (a size query).  A stream with no decodable frame is
+ * AA_ERR_INVALID; what aa_mp3_info declines is declined here. */
+int aa_mp3_index(const uint8_t* data, size_t len, aa_mp3_stream* stream, uint8_t* payload, int64_t payload_cap,
+                 int64_t* payload_bytes, aa_mp3_frame* frames, int64_t frame_cap);
+/* The decoder's table blob (csrc/aa_mp3_core.h Tables: |is|^(4/3), 2^(k/4),
+ * the IMDCT, matrixing and window values, the Huffman trees and band edges),
+ * built once on the host; aa_mp3_decode_device reads a device copy of exactly
+ * these bytes.  out NULL or cap short: AA_ERR_WORKSPACE with *bytes set. */
+int aa_mp3_tables(void* out, int64_t cap, int64_t* bytes);
+/* One restated table of the standard, read-only, as int32 values (the single
+ * copy: csrc/aa_mp3_tables.h).  kind / index:
+ *   0 Huffman code words, 1 their lengths: index = table number 1..31
+ *     (dim * dim values, pair (x, y) at x * dim + y), 32 / 33 = count1 table
+ *     A / B (16 values, v w x y as bits 3..0);
+ *   2 linbits (index 0: all 32);  3 slen1 (index 0) / slen2 (index 1);
+ *   4 pretab;  5 long and 6 short band edges (index: 0 44.1, 1 48, 2 32 kHz);
+ *   7 the synthesis window D * 65536 (512 values).
+ * *n: the values the table holds; AA_ERR_WORKSPACE when cap is short,
+ * AA_ERR_INVALID for a table that does not exist (0, 4, 14). */
+int aa_mp3_table(int32_t kind, int32_t index, int32_t* out, int64_t cap, int64_t* n);
+/* The core's polyphase synthesis alone, on the host: sb [n_slots][32] float64
+ * subband samples -> out [n_slots * 32] float64 (before the float32 rounding),
+ * slots before the first taken as zero.  (tests/test_mp3_tables.py) */
+int aa_mp3_synth_host(const double* sb, int64_t n_slots, double* out);
+/* AA_MP3_WG lanes (frame, channel) share a workgroup of the unpack launch. */
+#define AA_MP3_WG 64
+/* Workspace of one aa_mp3_decode_device / _frames_host over n_frames frames:
+ * the unpack slices (2.5 KB per frame and channel) and the float64 subband
+ * samples (4608 bytes per granule and channel, two channels held for every
+ * frame).  0 for n_frames <= 0. */
+size_t aa_mp3_device_workspace_bytes(int64_t n_frames);
+/* Decode n_frames frames of bytes[0, n_bytes) belonging to n_streams streams:
+ * stream k writes its `frames` interleaved frames at out_s16 + out_at
+ * (ffmpeg's s16: clip(lrint(x * 32768))) and / or out_f32 + out_at; either may
+ * be NULL; out_elems bounds both.  status[f * 4 + gr * 2 + ch] is an
+ * aa_mp3_status; a granule not AA_MP3_OK decodes as a zero spectrum, so the
+ * samples are defined for every status (the host decoder's, bit for bit).
+ * tables_dev: a device copy of aa_mp3_tables' bytes.  Three launches (unpack,
+ * hybrid, synth); allocates nothing; n_frames == 0 or n_streams == 0 is
+ * AA_OK; a short workspace AA_ERR_WORKSPACE. */
+int aa_mp3_decode_device(const void* tables_dev, const uint8_t* bytes_dev, int64_t n_bytes,
+                         const aa_mp3_frame* frames_dev, int64_t n_frames, const aa_mp3_stream* streams_dev,
+                         int64_t n_streams, int16_t* out_s16, float* out_f32, int64_t out_elems, int32_t* status_dev, void* workspace,
+                         size_t workspace_bytes, void* stream);
+/* The same phases as host loops, every pointer HOST memory: the host decoder. */
+int aa_mp3_decode_frames_host(const uint8_t* bytes, int64_t n_bytes, const aa_mp3_frame* frames, int64_t n_frames,
+                              const aa_mp3_stream* streams, int64_t n_streams, int16_t* out_s16, float* out_f32,
+                              int64_t out_elems, int32_t* status, void* workspace, size_t workspace_bytes);
+
 /* ---- file input of the batched corpus path (aa_amd/batch.py) ----
  * The whole file at path into buf (cap bytes; a pinned staging slot), in one
  * call: open, size, read, close -- the reference reads each file through
