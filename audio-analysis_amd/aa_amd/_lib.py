@@ -119,6 +119,16 @@ class SnComponent(C.Structure):
                 ("area", C.c_int32), ("order", C.c_int32)]
 
 
+class RsSegment(C.Structure):
+    """aa_rs_segment: one recording of an aa_resample_batch launch."""
+    _fields_ = [("src_off", C.c_int64), ("n_in", C.c_int64), ("dst_off", C.c_int64), ("n_out", C.c_int64),
+                ("kind", C.c_int32), ("channels", C.c_int32)]
+
+
+AA_RS_S16 = 0
+AA_RS_F32 = 1
+
+
 class FlacInfo(C.Structure):
     _fields_ = [("sample_rate", C.c_int32), ("channels", C.c_int32), ("bits_per_sample", C.c_int32),
                 ("total_frames", C.c_int64)]
@@ -284,6 +294,9 @@ _SIGS = {
     "aa_pcm_s16_to_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
     "aa_resample_poly": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                    C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    "aa_resample_batch": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int64,
+                                    C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
+                                    C.c_void_p]),
     "aa_sn_create": (C.c_int, [C.POINTER(SnConfig), C.POINTER(C.c_void_p)]),
     "aa_sn_destroy": (C.c_int, [C.c_void_p]),
     "aa_sn_geometry": (C.c_int, [C.POINTER(SnConfig), C.POINTER(C.c_int32)]),

@@ -191,7 +191,8 @@ def mp3_mode(mp3=None) -> str:
     return mode
 
 
-def decode_into(path, pool: SlotPool, flac="host", vorbis="host", mp3="host"):  # (BatchAnalyser passes its modes)
+def decode_into(path, pool: SlotPool, flac="host", vorbis="host", mp3="host",  # (BatchAnalyser passes its modes)
+                sr_out=SR, wav_any_rate=False, host_decode=None):
     """Decode one file; PCM16 48 kHz WAV lands in a pinned slot untouched, and
     with flac="gpu" an indexable FLAC file stays there compressed; with
     vorbis="gpu" an indexable Ogg Vorbis file stays there as its audio packets
@@ -199,7 +200,11 @@ def decode_into(path, pool: SlotPool, flac="host", vorbis="host", mp3="host"):  
     file as its flat main data (likewise).
     The file comes in with one aa_read_file call (stat, open, read, close
     without the interpreter lock: the decoder threads otherwise queued for it
-    behind the lanes' Python at every step)."""
+    behind the lanes' Python at every step).
+    The batched old-index path (aa_amd.ci_batch) analyses at ``sr_out`` = 16 kHz
+    and resamples every rate on the device, so it keeps a PCM16 WAV of any rate
+    in its slot (``wav_any_rate``) and decodes the rest with ``host_decode``
+    (path -> (mono f32, rate); default load_recording at the file's rate)."""
     import ctypes as C
     from . import identify_tracks as it
     from .audio import _is_flac
@@ -213,18 +218,23 @@ def decode_into(path, pool: SlotPool, flac="host", vorbis="host", mp3="host"):  
         try:
             buf = pool.np[i]
             w = _wav_pcm16(buf, got.value)
-            if w is not None and w[3] == SR:
+            if w is not None and (wav_any_rate or w[3] == SR):
                 off, nb, ch, sr = w
                 t = pool.t[i][off:off + nb].view(torch.int16)
-                return Decoded(n=nb // (2 * ch), sr=sr, s16=buf[off:off + nb].view(np.int16), s16_t=t,
-                               channels=ch, slot=i)
+                n_in = nb // (2 * ch)
+                n = n_in
+                if sr != sr_out:
+                    from .resample import out_length
+                    n = out_length(n_in, sr, sr_out)
+                return Decoded(n=n, sr=sr_out, s16=buf[off:off + nb].view(np.int16), s16_t=t,
+                               channels=ch, sr_in=sr, slot=i, n_in=n_in, path=str(path))
             if flac == "gpu" and _is_flac(buf, got.value):
                 from . import flac_gpu
                 from .resample import out_length
                 ix = flac_gpu.index(buf[:got.value])
                 if ix is not None and ix[0].total_frames > 0 and flac_gpu.fits_batch(ix[1]):
                     info, tab = ix
-                    return Decoded(n=out_length(info.total_frames, info.sample_rate, SR), sr=SR,
+                    return Decoded(n=out_length(info.total_frames, info.sample_rate, sr_out), sr=sr_out,
                                    channels=info.channels, sr_in=info.sample_rate, slot=i, flac=tab,
                                    comp_t=pool.t[i][:got.value], n_in=info.total_frames, path=str(path))
             if vorbis == "gpu" and got.value >= 4 and bytes(buf[:4]) == b"OggS":
@@ -234,7 +244,7 @@ def decode_into(path, pool: SlotPool, flac="host", vorbis="host", mp3="host"):  
                 if ix is not None and int(ix.stream["frames"][0]) > 0 and vorbis_gpu.fits_batch(ix):
                     st = ix.stream[0]
                     n_in, sr_in = int(st["frames"]), int(st["sample_rate"])
-                    return Decoded(n=out_length(n_in, sr_in, SR), sr=SR, channels=int(st["channels"]), sr_in=sr_in,
+                    return Decoded(n=out_length(n_in, sr_in, sr_out), sr=sr_out, channels=int(st["channels"]), sr_in=sr_in,
                                    slot=i, vorbis=ix, comp_t=pool.t[i][:ix.payload.size], n_in=n_in, path=str(path))
             if mp3 == "gpu":
                 from .audio import _is_mp3
@@ -245,7 +255,7 @@ def decode_into(path, pool: SlotPool, flac="host", vorbis="host", mp3="host"):  
                     if ix is not None and int(ix.stream["frames"][0]) > 0 and mp3_gpu.fits_batch(ix):
                         st = ix.stream[0]
                         n_in, sr_in = int(st["frames"]), int(st["sample_rate"])
-                        return Decoded(n=out_length(n_in, sr_in, SR), sr=SR, channels=int(st["channels"]),
+                        return Decoded(n=out_length(n_in, sr_in, sr_out), sr=sr_out, channels=int(st["channels"]),
                                        sr_in=sr_in, slot=i, mp3=ix, comp_t=pool.t[i][:ix.payload.size], n_in=n_in,
                                        path=str(path))
         except Exception:
@@ -253,10 +263,10 @@ def decode_into(path, pool: SlotPool, flac="host", vorbis="host", mp3="host"):  
             raise
     pool.put(i)  # (larger than a slot, or not a 48 kHz PCM16 WAV)
     # FLAC, other WAV encodings; other rates are resampled on the device at upload
-    frames, sr = it.load_recording(str(path), resample=None)
+    frames, sr = host_decode(str(path)) if host_decode else it.load_recording(str(path), resample=None)
     from .resample import out_length
-    return Decoded(n=out_length(len(frames), sr, SR), sr=SR, f32=np.ascontiguousarray(frames, dtype=np.float32),
-                   sr_in=sr)
+    return Decoded(n=out_length(len(frames), sr, sr_out), sr=sr_out,
+                   f32=np.ascontiguousarray(frames, dtype=np.float32), sr_in=sr, n_in=len(frames), path=str(path))
 
 
 class _Laps:
@@ -726,6 +736,17 @@ class BatchAnalyser:
         self.timing.lap("post", t)
         return docs
 
+    def _load(self, path, pool):
+        """(Decoded | the exception that stands for the file, sidecar meta) of one file, on a decoder thread."""
+        from .analyse import read_sidecar
+        meta = None
+        try:
+            meta = read_sidecar(path)
+            return decode_into(path, pool, self.flac, self.vorbis, self.mp3), meta
+        except Exception as e:
+            logging.error("Could not load %s", path, exc_info=True)
+            return Exception(f"Could not load {path}") if not isinstance(e, ValueError) else e, meta
+
     def run(self, jobs):
         """jobs: [(file_idx, path)] -> {file_idx: document} (the files of this rank)."""
         import threading
@@ -747,13 +768,7 @@ class BatchAnalyser:
 
         def load(job):
             idx, path = job
-            meta = None
-            try:
-                meta = read_sidecar(path)
-                return idx, path, decode_into(path, pool, self.flac, self.vorbis, self.mp3), meta
-            except Exception as e:
-                logging.error("Could not load %s", path, exc_info=True)
-                return idx, path, Exception(f"Could not load {path}") if not isinstance(e, ValueError) else e, meta
+            return (idx, path) + self._load(path, pool)
 
         results, errors = {}, []
         lock = threading.Lock()

@@ -12,6 +12,12 @@ holds every file's result in file order and writes the reference's sidecars
 file is classified by exactly the code a single process would run.
 
     python -m aa_amd.corpus FILE... [--bird-model PATH]* [--analyse-tracks B] [-o] [--gpus N]
+                            [--old-cacophony-index]
+
+``--old-cacophony-index`` (analyse.py's second mode, src/analyse.py:440-443)
+computes the old cacophony index of every file instead: no model is loaded,
+the files are sharded, gathered and written the same way, and with a GPU they
+go ``batch`` at a time through aa_amd.ci_batch.
 """
 from __future__ import annotations
 
@@ -91,8 +97,31 @@ def raise_hw_queues(n: int = 16):
         os.environ["GPU_MAX_HW_QUEUES"] = str(n)
 
 
+def _run_old_index(mine, batch, flac, vorbis, mp3, one_by_one):
+    """This rank's {file_idx: cacophony_index.calculate(file) plus
+    processing_time_seconds}: ``batch`` files per device pass (aa_amd.ci_batch),
+    or file by file."""
+    if not one_by_one:
+        from .ci_batch import CiBatchAnalyser
+        ba = CiBatchAnalyser(device=torch.device("cuda", torch.cuda.current_device()), batch=batch,
+                             lanes=default_lanes(), flac=flac, vorbis=vorbis, mp3=mp3)
+        return ba.run([(i, str(f)) for i, f in mine])
+    from . import cacophony_index
+    local = {}
+    for i, f in mine:
+        t0 = time.time()
+        try:
+            summary = cacophony_index.calculate(str(f))
+            summary["processing_time_seconds"] = round(time.time() - t0, 1)
+        except Exception as e:  # the failure stays with its file, as in run()
+            logging.error("Terminated with error", exc_info=True)
+            summary = {FAILED: f"{type(e).__name__}: {e}"}
+        local[i] = summary
+    return local
+
+
 def run(files, bird_models, analyse_tracks=False, examine_fn=None, rank=0, world=1, device=None, batch=16,
-        flac=None, vorbis=None, mp3=None):
+        flac=None, vorbis=None, mp3=None, old_cacophony_index=False):
     """Classify this rank's share of ``files``; returns {file_idx: summary}
     of ALL files on every rank (after the gather).  ``summary`` is what
     analyse.examine returns plus ``processing_time_seconds`` (src/analyse.py:451-453).
@@ -101,8 +130,15 @@ def run(files, bird_models, analyse_tracks=False, examine_fn=None, rank=0, world
     custom ``examine_fn`` runs them one by one.  ``flac``: where the batched
     path decodes FLAC files, "host" or "gpu" (batch.flac_mode; None: AA_FLAC);
     ``vorbis``: the same for Ogg Vorbis files (batch.vorbis_mode; None: AA_VORBIS);
-    ``mp3``: the same for MP3 files (batch.mp3_mode; None: AA_MP3)."""
+    ``mp3``: the same for MP3 files (batch.mp3_mode; None: AA_MP3).
+    ``old_cacophony_index``: each summary is cacophony_index.calculate's
+    document instead (``bird_models`` and ``analyse_tracks`` are ignored, as
+    analyse.py ignores them in that mode); batched under the same conditions,
+    else file by file through cacophony_index.calculate."""
     mine = shard.shard(list(files), rank, world)
+    if old_cacophony_index:
+        one_by_one = examine_fn is not None or not batch or not torch.cuda.is_available()
+        return gather_documents(_run_old_index(mine, batch, flac, vorbis, mp3, one_by_one), device=device)
     if examine_fn is None and batch and torch.cuda.is_available():
         from .batch import BatchAnalyser
         ba = BatchAnalyser(bird_models, analyse_tracks, device=torch.device("cuda", torch.cuda.current_device()),
@@ -189,7 +225,8 @@ def _worker(local_rank, world, args, port):
         dist.init_process_group(backend, device_id=dev if backend == "nccl" else None)
     try:
         gdev = dev if (world > 1 and dist.get_backend() == "nccl") else None
-        res = run(args.files, args.bird_model, args.analyse_tracks, rank=rank, world=world, device=gdev)
+        res = run(args.files, args.bird_model, args.analyse_tracks, rank=rank, world=world, device=gdev,
+                  old_cacophony_index=bool(args.old_cacophony_index))
         if rank == 0:
             write_results(args.files, res, to_stdout=bool(args.meta_to_stdout))
     finally:
@@ -201,6 +238,8 @@ def parse_args(argv=None):
     from .analyse import none_or_str, str2bool
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("files", nargs="+", help="audio files")
+    ap.add_argument("--old-cacophony-index", action="count",
+                    help="Calculate old cacophony index on these files")
     ap.add_argument("--bird-model", type=none_or_str, action="append", help="Path to bird model")
     ap.add_argument("--analyse-tracks", type=str2bool, default=False)
     ap.add_argument("-o", "--meta-to-stdout", action="count")

@@ -141,4 +141,14 @@ __device__ __forceinline__ int wave_or(int v) {
     return v;
 }
 
+// One frame of interleaved PCM16 (`ch` <= 8 channels at q) as load_recording
+// delivers it: ffmpeg's s16 -> librosa's buf_to_float (x / 32768, exact) and
+// the channel mean (numpy float32 sum in channel order, then one correctly
+// rounded division; the sum of <= 8 multiples of 2^-15 is exact).  Never -0.0.
+__device__ __forceinline__ float pcm_s16_frame_to_f32(const short* __restrict__ q, int ch) {
+    float s = (float)q[0] * (1.f / 32768.f);
+    for (int c = 1; c < ch; ++c) s = __fadd_rn(s, (float)q[c] * (1.f / 32768.f));
+    return ch == 1 ? s : __fdiv_rn(s, (float)ch);
+}
+
 }  // namespace aa

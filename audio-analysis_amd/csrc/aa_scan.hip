@@ -31,18 +31,13 @@ __global__ __launch_bounds__(256) void span_nonzero(const float* __restrict__ pc
     if (threadIdx.x == 0) flags[blockIdx.x] = any;
 }
 
-// ffmpeg's s16 samples -> librosa's buf_to_float (x / 32768, exact) and
-// load_recording's channel mean (numpy float32 sum in channel order, then one
-// correctly rounded division; the sum of <= 8 multiples of 2^-15 is exact).
-// One thread per output frame, 16-B stores of 4 frames where aligned.
+// ffmpeg's s16 samples -> mono f32 (pcm_s16_frame_to_f32, aa_common.h), one
+// thread per output frame.
 __global__ __launch_bounds__(256) void pcm_s16_to_f32(const short* __restrict__ in, long long n_frames, int ch,
                                                       float* __restrict__ out) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n_frames) return;
-    const short* q = in + i * ch;
-    float s = (float)q[0] * (1.f / 32768.f);
-    for (int c = 1; c < ch; ++c) s = __fadd_rn(s, (float)q[c] * (1.f / 32768.f));
-    out[i] = ch == 1 ? s : __fdiv_rn(s, (float)ch);
+    out[i] = pcm_s16_frame_to_f32(in + i * ch, ch);
 }
 
 }  // namespace aa

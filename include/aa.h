@@ -438,6 +438,37 @@ int aa_pcm_s16_to_f32(const int16_t* in, int64_t n_frames, int32_t channels, flo
 int aa_resample_poly(const float* x, int64_t n_in, const float* bank, int32_t L, int32_t M, int32_t taps,
                      int32_t half, float* y, int64_t n_out, void* stream);
 
+/* One recording of an aa_resample_batch launch: n_in frames of source `kind`
+ * starting at element src_off of that kind's buffer (AA_RS_S16: interleaved
+ * int16, `channels` (1..8) per frame; AA_RS_F32: mono f32, channels ignored),
+ * n_out output samples to y[dst_off ..). */
+#define AA_RS_S16 0
+#define AA_RS_F32 1
+typedef struct aa_rs_segment {
+    int64_t src_off, n_in, dst_off, n_out;
+    int32_t kind, channels;
+} aa_rs_segment;
+/* aa_resample_poly over n_seg (0..AA_CI_MAX_REC) recordings that share one
+ * filter, in one launch (the batched old-index path, aa_amd/ci_batch.py).
+ * Output m of a segment is, bit for bit, what aa_resample_poly gives on the
+ * segment's samples -- for an int16 segment on what aa_pcm_s16_to_f32 makes
+ * of them; no f32 copy at the source rate is written.  segs_dev: DEVICE array;
+ * max_n_out: the largest n_out in it (sizes the grid: outputs of a segment
+ * past max_n_out are not written).  src_s16 [n_s16 elements] / src_f32
+ * [n_f32] may be NULL when their size is 0.  A segment whose kind or channels
+ * is invalid, or whose source range leaves its buffer or whose output range
+ * leaves y[0, n_y), is skipped (nothing read or written): callers validate
+ * where they plan the table (aa_amd/ci_batch.plan_segments does).  Output
+ * ranges must not overlap.  Before any HIP call: a null segs_dev / bank / y,
+ * a null source with a non-zero size, negative sizes, n_seg outside
+ * 0..AA_CI_MAX_REC, max_n_out outside 0..n_y, L, M or taps < 1 (L, M > 65536),
+ * half >= L taps, or a filter whose tile does not fit LDS are AA_ERR_INVALID
+ * with the argument named in aa_last_error.  n_seg == 0, max_n_out == 0 and
+ * segments with n_out == 0 are AA_OK.  Allocates nothing; capturable. */
+int aa_resample_batch(const int16_t* src_s16, int64_t n_s16, const float* src_f32, int64_t n_f32,
+                      const aa_rs_segment* segs_dev, int32_t n_seg, int64_t max_n_out, const float* bank, int32_t L,
+                      int32_t M, int32_t taps, int32_t half, float* y, int64_t n_y, void* stream);
+
 /* ---------------------------------------------------------------- signal detector */
 /* signal_noise (src/identify_tracks.py:650-706): |STFT| (n_fft 4096) of the
  * recording, the 3x row/column-median mask, cv2 morphology, 8-connected

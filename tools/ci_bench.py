@@ -2,6 +2,7 @@
 against the reference's frame loop on this host.
 
     python tools/ci_bench.py [--seconds 60] [--batch 64] [--launches 30]
+                             [--resample-batch] [--corpus N] [--out PATH]
 
 HIP events around each launch set, after warm-up; the median and the fastest:
   * one clip of `seconds` at 16 kHz,
@@ -10,6 +11,17 @@ HIP events around each launch set, after warm-up; the median and the fastest:
 The host figure is the reference's loop on one clip, single thread: numpy's
 window product, scipy.fftpack.dct and Python's sum(x * x) per band, then the
 comparisons (src/cacophony_index.py:53-97).  Prints one JSON line.
+
+--resample-batch: aa_resample_batch over 16 staged int16 clips of `seconds`
+in one launch against the two-step way on the same buffers, 16 x
+(aa_pcm_s16_to_f32 + aa_resample_poly), from 48, 44.1 and 96 kHz to 16 kHz;
+the outputs are compared bit for bit first.
+--corpus N: N files of `seconds` as 48 kHz PCM16 WAV, then as MP3 with
+mp3="gpu": corpus.run(old_cacophony_index=True) against a loop of
+cacophony_index.calculate in the same process, three alternating pairs after
+one warm-up pair; and one CiBatchAnalyser run's phase times (wall and CPU time
+of the lane threads: wait_decode, to_16k, index, post).
+--out PATH: the JSON line also goes to PATH.
 """
 from __future__ import annotations
 
@@ -54,12 +66,117 @@ def timed(launch, launches):
     return {"median": float(np.median(ms)), "min": float(min(ms)), "max": float(max(ms))}
 
 
+def spread(v):
+    return {"median": float(np.median(v)), "min": float(min(v)), "max": float(max(v)), "n": len(v)}
+
+
+def resample_batch_bench(dev, seconds, launches, clips=16):
+    """{rate: timings} of one aa_resample_batch against clips x the two-step path."""
+    import torch
+
+    from aa_amd import _lib
+    from aa_amd.ci_batch import resample_batch
+    from aa_amd.resample import _bank, out_length
+    from tools import synth
+    L = _lib.lib()
+    out = {}
+    for sr in (48000, 44100, 96000):
+        x = synth.clip(5, seconds=seconds, sr=sr)
+        q = torch.from_numpy(np.round(x * 32768.0).astype(np.int16))
+        n_in, n_out = int(q.numel()), out_length(int(q.numel()), sr, 16000)
+        s16 = q.repeat(clips).to(dev)
+        tmp = torch.empty(n_in, dtype=torch.float32, device=dev)
+        y_two = torch.zeros(clips * n_out, dtype=torch.float32, device=dev)
+        y_one = torch.ones(clips * n_out, dtype=torch.float32, device=dev)
+        Lr, M, half, taps, bank = _bank(sr, 16000, dev)
+        segs = [_lib.RsSegment(src_off=k * n_in, n_in=n_in, dst_off=k * n_out, n_out=n_out, kind=_lib.AA_RS_S16,
+                               channels=1) for k in range(clips)]
+        segs_dev = torch.empty(clips * 40, dtype=torch.uint8, device=dev)
+        resample_batch(s16, None, segs, sr, y_one, segs_dev=segs_dev)  # (uploads the table once)
+        st = _lib.stream_ptr()
+        one_args = (_lib.dptr(s16), int(s16.numel()), None, 0, _lib.dptr(segs_dev), clips, n_out, _lib.dptr(bank), Lr,
+                    M, taps, half, _lib.dptr(y_one), int(y_one.numel()), st)
+
+        def one():
+            _lib.check(L.aa_resample_batch(*one_args), "aa_resample_batch")
+
+        def two():
+            for k in range(clips):
+                _lib.check(L.aa_pcm_s16_to_f32(_lib.dptr(s16) + 2 * k * n_in, n_in, 1, _lib.dptr(tmp), st), "widen")
+                _lib.check(L.aa_resample_poly(_lib.dptr(tmp), n_in, _lib.dptr(bank), Lr, M, taps, half,
+                                              _lib.dptr(y_two) + 4 * k * n_out, n_out, st), "aa_resample_poly")
+
+        one()
+        two()
+        torch.cuda.synchronize()
+        r = {"clips": clips, "n_in": n_in, "n_out": n_out, "L": Lr, "M": M, "taps": taps,
+             "bit_equal": bool(torch.equal(y_one.view(torch.int32), y_two.view(torch.int32))),
+             "two_step_ms": timed(two, launches), "batch_ms": timed(one, launches)}
+        r["speedup_median"] = r["two_step_ms"]["median"] / r["batch_ms"]["median"]
+        r["gfma_per_s_batch"] = clips * n_out * taps / (r["batch_ms"]["median"] * 1e-3) / 1e9
+        out[str(sr)] = r
+    return out
+
+
+def corpus_bench(dev, seconds, n_files, pairs=3):
+    """Batched corpus runs of the index against the per-file loop, WAV and MP3 (mp3="gpu")."""
+    import tempfile
+
+    from aa_amd import cacophony_index as ci
+    from aa_amd import corpus
+    from aa_amd.ci_batch import CiBatchAnalyser
+    from tools import synth
+    from tools.mp3_bench import make_clip
+    out = {}
+    with tempfile.TemporaryDirectory() as td:
+        td = Path(td)
+        kinds = {"wav": [], "mp3": []}
+        mp3 = make_clip(seconds)
+        for k in range(n_files):
+            p = td / f"c{k}.wav"
+            synth.write_wav(p, synth.clip(100 + k % 8, seconds=seconds, sr=48000), sr=48000)
+            kinds["wav"].append(str(p))
+            p = td / f"c{k}.mp3"
+            p.write_bytes(mp3)
+            kinds["mp3"].append(str(p))
+        for kind, files in kinds.items():
+            loop, batched, same = [], [], True
+            for rnd in range(pairs + 1):  # the first pair warms both paths up (pinned slots, banks, plans)
+                t0 = time.perf_counter()
+                single = {k: ci.calculate(f) for k, f in enumerate(files)}
+                t1 = time.perf_counter()
+                res = corpus.run(files, None, mp3="gpu", old_cacophony_index=True)
+                t2 = time.perf_counter()
+                same &= all({kk: v for kk, v in res[k].items() if kk != "processing_time_seconds"} == single[k]
+                            for k in single)
+                if rnd:
+                    loop.append((t1 - t0) * 1e3)
+                    batched.append((t2 - t1) * 1e3)
+            ba = CiBatchAnalyser(device=dev, batch=16, lanes=corpus.default_lanes(), mp3="gpu")
+            t0 = time.perf_counter()
+            ba.run(list(enumerate(files)))
+            wall = (time.perf_counter() - t0) * 1e3
+            out[kind] = {"files": n_files, "documents_equal": bool(same), "loop_ms": spread(loop),
+                         "batched_ms": spread(batched),
+                         "speedup_median": float(np.median(loop) / np.median(batched)),
+                         "phases": {"wall_ms": wall, "lanes": min(ba.n_lanes, -(-n_files // 16)),
+                                    "lane_wall_ms": {k: 1e3 * v for k, v in ba.timing.t.items()},
+                                    "lane_cpu_ms": {k: 1e3 * v for k, v in ba.timing.cpu.items()}}}
+    return out
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=60.0)
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--launches", type=int, default=30)
+    ap.add_argument("--resample-batch", action="store_true")
+    ap.add_argument("--corpus", type=int, default=0, help="files of the corpus comparison (0: skip)")
+    ap.add_argument("--out", default=None, help="also write the JSON line here")
     a = ap.parse_args()
+    if a.corpus:
+        from aa_amd.corpus import raise_hw_queues
+        raise_hw_queues()  # as python -m aa_amd.corpus does, before the first GPU call
 
     import ctypes as C
 
@@ -121,7 +238,14 @@ def main() -> None:
         resample_device(d48, 48000, ci.SAMPLE_RATE, out=buf)
         index()
     out["gpu_ms_resample_48k_plus_1_clip"] = timed(resampled, a.launches)
+    if a.resample_batch:
+        out["resample_batch"] = resample_batch_bench(dev, a.seconds, a.launches)
+    if a.corpus:
+        out["corpus"] = corpus_bench(dev, a.seconds, a.corpus)
     print(json.dumps(out))
+    if a.out:
+        Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(a.out).write_text(json.dumps(out, indent=1) + "\n")
 
 
 if __name__ == "__main__":
