@@ -18,7 +18,8 @@
 //   * the split-bf16 kernel families, each in its own header: aa_conv_x3.h
 //     (direct; it also holds the fragment helpers -- x3_mfma3, x3_frag_pixel,
 //     x3_bofs, x3_read_b, x3_stage_split, x3_step_jit -- and the epilogue
-//     x3_store that the next two share), aa_conv_wg.h (Winograd along W),
+//     x3_store that the next three share), aa_conv_pair.h (the 3x3 32 -> 64
+//     and 64 -> 64 convs in one launch), aa_conv_wg.h (Winograd along W),
 //     aa_conv_tail.h (last conv + head in one launch), aa_gconv.h
 //     (runtime-shaped; also built into aa_graph.hip, so it keeps its own);
 //   * aa_cnn_plan.h: Stage, Model and the host-only planner (layer list ->
@@ -1090,6 +1091,7 @@ __global__ void track_mean(const float* __restrict__ probs, int n_models, long l
 }  // namespace aa
 
 #include "aa_conv_x3.h"
+#include "aa_conv_pair.h"
 #include "aa_conv_wg.h"
 #include "aa_gconv.h"
 #include "aa_conv_tail.h"
@@ -1204,6 +1206,24 @@ static int launch_wg(const Stage& s, const void* in, void* out, int n, hipStream
         hipLaunchKernelGGL(k, grid, dim3(WM * WN * 64), lds, st, (const float*)in, s.Hin, s.Win, (const bf16*)s.d_w,
                            s.d_b, (float*)out, s.Hout, s.Wout, s.cout, tiles_w, s.act, s.alpha);
     });
+}
+
+// Stages a and b (3x3 32 -> 64, 3x3 64 -> 64; aa_cnn_plan.h mark_pairs) in one
+// launch: reads a's input, writes b's output
+static int launch_pair(const Stage& a, const Stage& b, const void* in, void* out, int n, hipStream_t st) {
+    AA_CHECK((double)a.Hin * a.Win * a.cin * 4 < 2147483647.0, AA_ERR_UNSUPPORTED,
+             "conv %s: one window's activations exceed 2 GiB", a.name.c_str());
+    constexpr size_t lds = pair_lds_bytes<PAIR_TH, PAIR_TW, true>();
+    auto go = [&](auto is) {
+        auto k = conv_x3_pair<PAIR_TH, PAIR_TW, 2, true, true, 3, true, decltype(is)::value>;
+        return launch_tuned(b, nullptr, n, (const void*)k, lds, true, 1, PAIR_TH, PAIR_TW, 64,
+                            [&](dim3 grid, int tiles_w, const FirstConv&) {
+            hipLaunchKernelGGL(k, grid, dim3(256), lds, st, (const float*)in, a.Hin, a.Win, (const bf16*)a.d_w, a.d_b,
+                               a.act, a.alpha, (const bf16*)b.d_w, b.d_b, (float*)out, b.Hout, b.Wout, b.cout, tiles_w,
+                               b.act, b.alpha);
+        });
+    };
+    return a.in_split ? go(std::true_type{}) : go(std::false_type{});
 }
 
 // A split-bf16 stage's runtime (fused_first, in_split, out_split) as template
@@ -1414,17 +1434,30 @@ static int run_stages_t(Model* m, const void* x, int n, int last_stage, float* l
                     static_cast<char*>(workspace) + align_up(m->act_elems[0] * es * n, 256)};
     float* tmp = reinterpret_cast<float*>(buf[1] + align_up(m->act_elems[1] * es * n, 256));
     const void* in = x;
+    int flip = 0;  // after a pair the later stages write the buffer of the other parity (mark_pairs)
     for (int k = 0; k <= last_stage; ++k) {
         const Stage& s = m->st[k];
         if (s.skipped) continue;  // computed inside stage k + 1 (reads x directly)
+        if (k + 1 <= last_stage && m->st[k + 1].pair) continue;  // computed inside stage k + 1 (conv_x3_pair)
         // (a fused tail writes its per-tile maxima into the skipped conv stage's
-        // buffer: its own would be the one its input lives in)
-        void* out = buf[(s.tail ? k - 1 : k) % 2];
+        // buffer: its own would be the one its input lives in; so does a pair,
+        // whose own buffer holds the previous stage's input)
+        void* out = buf[((s.tail || s.pair ? k - 1 : k) % 2) ^ flip];
         const Stage* first = (s.fused_first || s.tail) ? &m->st[k - 1] : nullptr;
         hipEvent_t e0 = nullptr;
         int rc = timed ? m->timer.begin(k, st, &e0) : AA_OK;
         if (rc != AA_OK) return rc;
-        rc = launch_stage<T>(*m, s, in, out, logits, probs, n, st, first, tmp);
+        if (s.pair) {
+            if constexpr (is_split<T>()) {
+                rc = launch_pair(m->st[k - 1], s, in, out, n, st);
+                flip ^= 1;
+            } else {
+                set_error("%s: the fused conv pair is split-bf16 only", s.name.c_str());
+                rc = AA_ERR_UNSUPPORTED;
+            }
+        } else {
+            rc = launch_stage<T>(*m, s, in, out, logits, probs, n, st, first, tmp);
+        }
         if (rc != AA_OK) return rc;
         rc = m->timer.end(k, st, e0);
         if (rc != AA_OK) return rc;

@@ -8,8 +8,9 @@
 // plan_model folds each BatchNormalization into the preceding conv, fuses the
 // activation and a following max-pool into the conv's epilogue, and the final
 // 1x1 conv + GlobalMaxPool2D + sigmoid into one head stage; then the fusion
-// passes (first conv, split hand-off, tail) run over the stage vector and the
-// ping-pong workspace is sized.
+// passes (first conv, split hand-off, tail) run over the stage vector, the
+// ping-pong workspace is sized, and the 3x3 conv pairs that run as one launch
+// within that workspace are marked (mark_pairs).
 #pragma once
 
 #include <algorithm>
@@ -62,6 +63,7 @@ struct Stage {
     int cin_pad = 0;      // ST_GCONV: C_in rounded up to 32
     int tail = 0;         // ST_HEAD, split-bf16: computes the previous conv stage itself (aa_conv_tail.h)
     void* d_tw = nullptr;  // tail: head weights packed per wave / label fragment, hi then lo
+    int pair = 0;         // split-bf16: a full forward computes the previous stage inside this one (aa_conv_pair.h)
 };
 
 struct Model {
@@ -395,6 +397,59 @@ static void size_workspace(Model& m) {
     }
 }
 
+// per-window elements stage k writes into its activation buffer (what
+// size_workspace reserved for it)
+static size_t stage_out_elems(const Model& m, size_t k) {
+    const size_t es = prec_bytes(m.prec);
+    const Stage& s = m.st[k];
+    if (k + 1 == m.st.size()) {
+        if (s.kind != ST_HEAD) return 0;
+        if (s.tail) {
+            const Stage& c = m.st[k - 1];
+            const size_t tiles = (size_t)((c.Hc + TAIL_TH - 1) / TAIL_TH) * ((c.Wc + TAIL_TW - 1) / TAIL_TW);
+            return (tiles * 32 * sizeof(float) + es - 1) / es;
+        }
+        return ((((size_t)s.Hin * s.Win + 63) / 64) * s.cout_pad * sizeof(float) + es - 1) / es;
+    }
+    if (s.skipped || s.kind == ST_POOLDENSE) return 0;
+    return (size_t)s.Hout * s.Wout * s.cout;
+}
+
+// split-bf16: a 3x3 32 -> 64 conv_x3 stage that hands its output to a 3x3
+// 64 -> 64 conv_x3 stage in the split layout, neither pooled: a full forward
+// runs both in one launch (conv_x3_pair) and stage k's activations never
+// reach HBM.  Only the consumer is marked: the stage vector, names, flops,
+// bytes, split flags and workspace stay as planned, and a prefix that ends at
+// stage k still runs its own kernel.
+//
+// Buffers: stage k + 1's ping-pong buffer is the one stage k's input lives
+// in, so the pair writes stage k's buffer instead (stage k + 1's output is
+// the smaller), and every later stage then writes the buffer of the other
+// parity.  The pair is marked only where each of those outputs fits the
+// buffer it lands in.  AA_X3_PAIR=0 at create time keeps the two launches.
+static void mark_pairs(Model& m) {
+    const char* e = getenv("AA_X3_PAIR");
+    if (e && e[0] == '0') return;
+    int flip = 0;  // later stages write the other buffer
+    for (size_t k = 0; k + 1 < m.st.size(); ++k) {
+        const Stage& a = m.st[k];
+        Stage& b = m.st[k + 1];
+        if (a.skipped || a.fused_first || a.pair || a.kind != ST_MFMA || b.kind != ST_MFMA) continue;
+        if (!(a.kh == 3 && a.kw == 3 && a.cin == 32 && a.cout == 64 && a.cout_pad == 64 && a.pool == 1 && !a.wg &&
+              a.out_split && b.kh == 3 && b.kw == 3 && b.cin == 64 && b.cout_pad == 64 && b.pool == 1 && !b.wg &&
+              b.in_split && !b.out_split))
+            continue;
+        bool fits = stage_out_elems(m, k + 1) <= m.act_elems[(k % 2) ^ flip];
+        for (size_t j = k + 2; fits && j < m.st.size(); ++j) {
+            const size_t dst = (m.st[j].tail ? j - 1 : j) % 2;
+            fits = stage_out_elems(m, j) <= m.act_elems[dst ^ flip ^ 1];
+        }
+        if (!fits) continue;
+        b.pair = 1;
+        flip ^= 1;
+    }
+}
+
 // The arguments of aa_model_create -> a Model whose stages hold their host
 // images (no device memory).  On failure *out is untouched and the reason is
 // in aa_last_error.
@@ -452,6 +507,7 @@ static int plan_model(const aa_layer* layers, int32_t n_layers, const float* blo
     m->L = st.back().cout;
     m->st = std::move(st);
     size_workspace(*m);
+    if (precision == AA_PREC_BF16X3) mark_pairs(*m);
     *out = m;
     return AA_OK;
 }

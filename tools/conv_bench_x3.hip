@@ -294,6 +294,155 @@ int main(int argc, char** argv) {
             }
         return bad ? 1 : 0;
     }
+    if (which == 40 || which == 41) {
+        // The 3x3 32->64 (split out) and 64->64 (split in, f32 out) convs at model1's shape: the two
+        // shipped conv_x3 launches back to back ("chain") against conv_x3_pair (aa_conv_pair.h), on
+        // grouped-split N(0,1) activations, split N(0,0.05) weights packed with their swizzle and
+        // N(0,0.1) biases.  40: every pair variant's output compared word for word with the chain's,
+        // then 5 alternating rounds of 20 launches.  41 V: variant V alone (0: chain), 2 launches
+        // (PMC passes).
+        const int Hin = 52, Win = 74, Hm = 50, Wm = 72, Ho = 48, Wo = 70;
+        const size_t in_el = (size_t)n * Hin * Win * 32, mid_el = (size_t)n * Hm * Wm * 64, on = (size_t)n * Ho * Wo * 64;
+        float *bA, *bB;
+        void *wA, *wB, *mid, *out2;
+        (void)hipMalloc(&bA, 256);
+        (void)hipMalloc(&bB, 256);
+        (void)hipMalloc(&wA, 9 * 64 * 128);
+        (void)hipMalloc(&wB, 18 * 64 * 128);
+        (void)hipMalloc(&mid, mid_el * 4);
+        (void)hipMalloc(&out2, on * 4);
+        {
+            unsigned st = 1;
+            auto gauss = [&]() {
+                float a = 0;
+                for (int k = 0; k < 4; ++k) { st = st * 1664525u + 1013904223u; a += (st >> 8) * (1.f / 16777216.f) - 0.5f; }
+                return a * 1.7f;
+            };
+            auto split = [](float x, uint16_t& hi, uint16_t& lo) {
+                uint32_t u; memcpy(&u, &x, 4);
+                uint32_t r = (u + 0x7fff + ((u >> 16) & 1)) & 0xffff0000u;
+                float hf; memcpy(&hf, &r, 4);
+                float l = x - hf; uint32_t v; memcpy(&v, &l, 4);
+                v = (v + 0x7fff + ((v >> 16) & 1)) >> 16;
+                hi = (uint16_t)(r >> 16); lo = (uint16_t)v;
+            };
+            std::vector<uint16_t> hs(in_el * 2);  // grouped split: per pixel 32 hi then 32 lo
+            for (size_t px = 0; px < in_el / 32; ++px)
+                for (int c = 0; c < 32; ++c) split(gauss(), hs[px * 64 + c], hs[px * 64 + 32 + c]);
+            (void)hipMemcpy(in, hs.data(), hs.size() * 2, hipMemcpyHostToDevice);
+            // packed weights: per step 64 rows of 8 units, unit u (hi 0-3, lo 4-7) of row o in slot (u + o) & 7
+            auto pack = [&](int steps, void* dst) {
+                std::vector<uint16_t> ws((size_t)steps * 64 * 64);
+                for (int s = 0; s < steps; ++s)
+                    for (int o = 0; o < 64; ++o)
+                        for (int c = 0; c < 32; ++c) {
+                            uint16_t hi, lo;
+                            split(0.05f * gauss(), hi, lo);
+                            const size_t row = ((size_t)s * 64 + o) * 64;
+                            ws[row + (((c >> 3) + o) & 7) * 8 + (c & 7)] = hi;
+                            ws[row + (((c >> 3) + 4 + o) & 7) * 8 + (c & 7)] = lo;
+                        }
+                (void)hipMemcpy(dst, ws.data(), ws.size() * 2, hipMemcpyHostToDevice);
+            };
+            pack(9, wA);
+            pack(18, wB);
+            std::vector<float> hb(64);
+            for (auto& x : hb) x = 0.1f * gauss();
+            (void)hipMemcpy(bA, hb.data(), 256, hipMemcpyHostToDevice);
+            for (auto& x : hb) x = 0.1f * gauss();
+            (void)hipMemcpy(bB, hb.data(), 256, hipMemcpyHostToDevice);
+        }
+        // the chain: the shipped tiles (aa_cnn_tiles.h AA_X3_CFGS)
+        auto kA = conv_x3<3, 3, 32, 4, 2, 3, 2, 1, 10, 18, false, 0, true, false, 4, true, true>;
+        auto kB = conv_x3<3, 3, 64, 2, 2, 3, 2, 1, 12, 8, false, 0, true, true, 0, true, false>;
+        const size_t lA = x3_lds_bytes<3, 3, 32, 64, 10, 18, false, true>(), lB = x3_lds_bytes<3, 3, 64, 64, 12, 8, false, true>();
+        (void)hipFuncSetAttribute((const void*)kA, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lA);
+        (void)hipFuncSetAttribute((const void*)kB, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lB);
+        const int twA = (Wm + 17) / 18, thA = (Hm + 9) / 10, twB = (Wo + 7) / 8, thB = (Ho + 11) / 12;
+        auto chainA = [&]() {
+            hipLaunchKernelGGL(kA, dim3(thA * twA, 1, n), dim3(512), lA, 0, (const float*)in, Hin, Win, (const bf16*)wA, bA,
+                               (float*)mid, Hm, Wm, 64, twA, 1, 0.3f, fc);
+        };
+        auto chainB = [&](void* o) {
+            hipLaunchKernelGGL(kB, dim3(thB * twB, 1, n), dim3(256), lB, 0, (const float*)mid, Hm, Wm, (const bf16*)wB, bB,
+                               (float*)o, Ho, Wo, 64, twB, 1, 0.3f, fc);
+        };
+        // pair variants: (B sets in flight, A just in time, pinned schedule, pinned waves per SIMD)
+#define PAIRK(BDV, JV, PV, OV, AL) (const void*)conv_x3_pair<12, 8, BDV, JV, PV, OV, AL>
+        // (first sweep, group images beside the patch, 2 blocks per CU: bd2 jit pin 83.5, bd3 jit pin 82.8,
+        // bd2 jit free 87.1, bd2 ahead free 84.9, bd4 jit pin 83.1 us against the chain's 84.1)
+        constexpr int NV = 8;
+        const void* ks[NV] = {PAIRK(2, true, true, 2, false), PAIRK(2, false, true, 0, false), PAIRK(3, false, true, 0, false),
+                              PAIRK(2, true, true, 3, true),  PAIRK(2, true, true, 4, true),   PAIRK(3, true, true, 3, true),
+                              PAIRK(2, true, false, 4, true), PAIRK(2, false, true, 3, true)};
+        const char* kn[NV] = {"bd2 jit pin occ2", "bd2 ahead pin", "bd3 ahead pin", "alias bd2 jit pin occ3", "alias bd2 jit pin occ4",
+                              "alias bd3 jit pin occ3", "alias bd2 jit free occ4", "alias bd2 ahead pin occ3"};
+        const size_t lds_of[NV] = {pair_lds_bytes<12, 8, false>(), pair_lds_bytes<12, 8, false>(), pair_lds_bytes<12, 8, false>(),
+                                   pair_lds_bytes<12, 8, true>(),  pair_lds_bytes<12, 8, true>(),  pair_lds_bytes<12, 8, true>(),
+                                   pair_lds_bytes<12, 8, true>(),  pair_lds_bytes<12, 8, true>()};
+        for (int v = 0; v < NV; ++v) (void)hipFuncSetAttribute(ks[v], hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_of[v]);
+        auto pair = [&](int v, void* o) {
+            const float* fin = (const float*)in;
+            const bf16 *fa = (const bf16*)wA, *fb = (const bf16*)wB;
+            float* fo = (float*)o;
+            int hin = Hin, win = Win, ho = Ho, wo = Wo, co = 64, tws = twB, act = 1;
+            float alpha = 0.3f;
+            void* args[] = {&fin, &hin, &win, &fa, &bA, &act, &alpha, &fb, &bB, &fo, &ho, &wo, &co, &tws, &act, &alpha};
+            (void)hipLaunchKernel(ks[v], dim3(thB * twB, 1, n), dim3(256), args, lds_of[v], 0);
+        };
+        if (which == 41) {
+            const int v = argc > 2 ? atoi(argv[2]) : 0;
+            for (int i = 0; i < 2; ++i) {
+                if (v == 0) { chainA(); chainB(out); }
+                else pair(v - 1, out2);
+            }
+            const hipError_t e = hipDeviceSynchronize();
+            printf("variant %d (%s): %s\n", v, v ? kn[v - 1] : "chain", hipGetErrorString(e));
+            return e != hipSuccess;
+        }
+        printf("LDS: chain A %zu, chain B %zu, pair %zu, pair alias %zu\n", lA, lB, lds_of[0], lds_of[3]);
+        std::vector<uint32_t> ref(on), c(on);
+        (void)hipMemset(out, 0xff, on * 4);
+        chainA();
+        chainB(out);
+        if (hipDeviceSynchronize() != hipSuccess) { printf("kernel error (chain)\n"); return 2; }
+        (void)hipMemcpy(ref.data(), out, on * 4, hipMemcpyDeviceToHost);
+        size_t bad = 0;
+        for (int v = 0; v < NV; ++v) {
+            (void)hipMemset(out2, 0xee, on * 4);
+            pair(v, out2);
+            if (hipDeviceSynchronize() != hipSuccess) { printf("kernel error (pair %s)\n", kn[v]); return 2; }
+            (void)hipMemcpy(c.data(), out2, on * 4, hipMemcpyDeviceToHost);
+            size_t nd = 0;
+            for (size_t i = 0; i < on; ++i) nd += ref[i] != c[i];
+            printf("pair %-24s: %zu of %zu output words differ from the chain\n", kn[v], nd, on);
+            bad += nd;
+        }
+        hipEvent_t e0, e1;
+        (void)hipEventCreate(&e0);
+        (void)hipEventCreate(&e1);
+        auto timed = [&](const char* name, int round, auto&& f) {
+            for (int i = 0; i < 2; ++i) f();
+            (void)hipEventRecord(e0, 0);
+            for (int i = 0; i < it; ++i) f();
+            (void)hipEventRecord(e1, 0);
+            (void)hipEventSynchronize(e1);
+            float ms = 0;
+            (void)hipEventElapsedTime(&ms, e0, e1);
+            printf("round %d %-30s %7.1f us\n", round, name, 1e3f * ms / it);
+        };
+        for (int round = 0; round < 5; ++round) {
+            timed("chain A (32->64)", round, [&]() { chainA(); });
+            timed("chain B (64->64)", round, [&]() { chainB(out); });
+            timed("chain A + B", round, [&]() { chainA(); chainB(out); });
+            for (int v = 0; v < NV; ++v) {
+                char nm[48];
+                snprintf(nm, sizeof nm, "pair %s", kn[v]);
+                timed(nm, round, [&]() { pair(v, out2); });
+            }
+        }
+        return bad ? 1 : 0;
+    }
     if (which == 32 || which == 33) {  // conv_wg (channel split) vs conv_wgp (plane split): outputs compared, then timed
         const int iters = which == 33 ? 2 : it;
         const int Hin = 48, Win = 70, cout = 128, Hc = Hin - 8, Wc = Win - 2, Hout = Hc / 3, Wout = Wc / 3;
