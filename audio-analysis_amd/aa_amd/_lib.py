@@ -264,6 +264,7 @@ _SIGS = {
                                 C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
     "aa_model_stage_image": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t,
                                        C.POINTER(C.c_size_t)]),
+    "aa_model_first_lane_image": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "aa_graph_create": (C.c_int, [C.POINTER(Node), C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
                                   C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
     "aa_graph_destroy": (C.c_int, [C.c_void_p]),

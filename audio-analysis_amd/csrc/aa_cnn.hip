@@ -312,6 +312,7 @@ struct FirstConv {
     float mag_exp;
     int H0, W0;      // log-mel image
     int lm_f16;      // log-mel stored as float16 (aa_model_set_input_f16)
+    const void* img; // conv_x3: the per-lane image of w and b (aa_cnn_pack.h pack_first_lanes)
 };
 
 // one log-mel value of the fused first conv's input (f32, or f16 when lm_f16)
@@ -1155,7 +1156,7 @@ static int launch_tuned(const Stage& s, const Stage* first, int n, const void* k
     if (first) {
         const float slope = first->act == ACT_LEAKY ? first->alpha : first->act == ACT_RELU ? 0.f : 1.f;
         fc = FirstConv{(const float*)first->d_w, first->d_b, first->act, slope, first->has_mag,
-                       first->mag_exp, first->Hin, first->Win, s.lm_f16};
+                       first->mag_exp, first->Hin, first->Win, s.lm_f16, s.d_f1};
     }
     AA_CHECK(lds <= 160 * 1024, AA_ERR_UNSUPPORTED, "conv %s: %zu B LDS", s.name.c_str(), lds);
     AA_DYN_LDS(kernel, lds);
@@ -1183,9 +1184,22 @@ static int launch_mfma(const Stage& s, const void* in, void* out, int n, hipStre
 }
 
 template <int KH, int KW, int CIN, int WM, int WN, int MF, int NF, int POOL, int TH, int TW, bool RING, bool AJIT,
-          int OCC, bool FUSED, bool IN_SPLIT, bool OUT_SPLIT>
+          int OCC, bool FUSED, bool IN_SPLIT, bool OUT_SPLIT, int LM = 0>
 static int launch_x3(const Stage& s, const void* in, void* out, int n, hipStream_t st, const Stage* first) {
-    auto k = conv_x3<KH, KW, CIN, WM, WN, MF, NF, POOL, TH, TW, FUSED, 0, RING, AJIT, OCC, IN_SPLIT, OUT_SPLIT>;
+    // a fused first conv (launch_stage: pool 3 only): the instantiation for
+    // its log-mel form (conv_x3's LM)
+    if constexpr (FUSED && LM == 0 && POOL == 3) {
+        const int lm = (s.lm_f16 ? 1 : 0) | (first && first->has_mag ? 2 : 0);
+#define AA_X3_LM(V)                                                                                              \
+        if (lm == V)                                                                                             \
+            return launch_x3<KH, KW, CIN, WM, WN, MF, NF, POOL, TH, TW, RING, AJIT, OCC, FUSED, IN_SPLIT, OUT_SPLIT, V>( \
+                s, in, out, n, st, first);
+        AA_X3_LM(1) AA_X3_LM(2) AA_X3_LM(3)
+#undef AA_X3_LM
+    }
+    if constexpr (FUSED)
+        AA_CHECK(s.d_f1, AA_ERR_INVALID, "conv %s: no first-layer lane image", s.name.c_str());
+    auto k = conv_x3<KH, KW, CIN, WM, WN, MF, NF, POOL, TH, TW, FUSED, 0, RING, AJIT, OCC, IN_SPLIT, OUT_SPLIT, LM>;
     constexpr int BN = WN * NF * 16;
     const size_t lds = x3_lds_bytes<KH, KW, CIN, BN, TH, TW, FUSED, RING>();
     return launch_tuned(s, FUSED ? first : nullptr, n, (const void*)k, lds, true, POOL, TH, TW, BN,
@@ -1398,6 +1412,7 @@ static void free_model(Model* m) {
             (void)hipFree(s.d_w);
             (void)hipFree(s.d_b);
             (void)hipFree(s.d_tw);
+            (void)hipFree(s.d_f1);
         }
     delete m;
 }
@@ -1415,9 +1430,11 @@ static int upload_model(Model* m) {
         if (e == hipSuccess) e = put((void**)&s.d_b, s.h_b.data(), sizeof(float) * s.h_b.size());
         AA_CHECK(e == hipSuccess, AA_ERR_HIP, "aa_model_create: layer %d: %s", s.layer_end, hipGetErrorString(e));
         if (!s.h_tw.empty()) e = put(&s.d_tw, s.h_tw.data(), s.h_tw.size());
+        if (e == hipSuccess && !s.h_f1.empty()) e = put(&s.d_f1, s.h_f1.data(), s.h_f1.size());
         AA_CHECK(e == hipSuccess, AA_ERR_HIP, "aa_model_create: %s", hipGetErrorString(e));
         std::vector<uint8_t>().swap(s.h_w);
         std::vector<uint8_t>().swap(s.h_tw);
+        std::vector<uint8_t>().swap(s.h_f1);
         std::vector<float>().swap(s.h_b);
     }
     return AA_OK;
@@ -1501,6 +1518,20 @@ extern "C" int aa_model_create(const aa_layer* layers, int32_t n_layers, const f
         return rc;
     }
     *model = m;
+    return AA_OK;
+}
+
+extern "C" int aa_model_first_lane_image(const void* model, void* buf, size_t cap, size_t* len) {
+    const Model* m = static_cast<const Model*>(model);
+    AA_CHECK(m && len, AA_ERR_INVALID, "aa_model_first_lane_image: bad argument");
+    AA_CHECK(!m->uploaded, AA_ERR_UNSUPPORTED,
+             "aa_model_first_lane_image: the host images are released once a model is created; plan it (aa_model_plan)");
+    static const std::vector<uint8_t> none;
+    const std::vector<uint8_t>& img = m->st.size() >= 2 ? m->st[1].h_f1 : none;
+    *len = img.size();
+    if (!buf) return AA_OK;  // a size query
+    AA_CHECK(cap >= *len, AA_ERR_INVALID, "aa_model_first_lane_image: buffer %zu < %zu", cap, *len);
+    if (*len) memcpy(buf, img.data(), *len);
     return AA_OK;
 }
 

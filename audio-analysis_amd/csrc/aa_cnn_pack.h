@@ -51,6 +51,39 @@ static inline uint8_t f2fp8(float f) {
     return sgn | (uint8_t)(((ee + 7) << 3) | ((int)q - 8));
 }
 
+// The per-lane constants of the fused first conv in the split-bf16 kernel
+// (aa_conv_x3.h, FUSED): what a lane of a wave holds while it computes the
+// first layer with two v_mfma_f32_32x32x16_bf16, built once per model instead
+// of once per wave.  [part][lane 0..63][16 B]: part 0 the lane's A operand of
+// MFMA 1 (8 bf16), part 1 that of MFMA 2, parts 2..5 its 16 accumulator start
+// values (the bias, f32).  w: the folded first-layer weights [32][9], b: [32].
+// MFMA row m = lane & 31 computes first-layer channel
+// 16 ((m >> 2) & 1) + 4 (m >> 3) + (m & 3); k-group kg = lane >> 5.  The 27
+// split products of a pixel sit in the 32 k-slots of the two MFMAs: MFMA 1 =
+// wh.xh (k-group 0) and wh.xl (k-group 1) over taps 0-7, so both k-groups
+// hold the weights' hi halves; MFMA 2 = wl.xh over taps 0-7 (k-group 0) and
+// wh8.xh8, wh8.xl8, wl8.xh8, then zeros (k-group 1).  D register r of a
+// k-group kg lane holds channel 16 kg + r.
+constexpr int F1_LANE_PARTS = 6;
+constexpr size_t F1_LANE_IMAGE_BYTES = (size_t)F1_LANE_PARTS * 64 * 16;
+static inline std::vector<uint8_t> pack_first_lanes(const float* w, const float* b) {
+    std::vector<uint8_t> img(F1_LANE_IMAGE_BYTES);
+    auto lo = [](float x) { return f2bf(x - bf2f(f2bf(x))); };
+    for (int lane = 0; lane < 64; ++lane) {
+        const int l32 = lane & 31, kg = lane >> 5;
+        const float* w9 = w + (16 * ((l32 >> 2) & 1) + 4 * (l32 >> 3) + (l32 & 3)) * 9;
+        uint16_t wa[8], wal[8];
+        for (int j = 0; j < 8; ++j) {
+            wa[j] = f2bf(w9[j]);
+            wal[j] = kg == 0 ? lo(w9[j]) : j < 2 ? f2bf(w9[8]) : j == 2 ? lo(w9[8]) : (uint16_t)0;
+        }
+        memcpy(&img[(0 * 64 + lane) * 16], wa, 16);
+        memcpy(&img[(1 * 64 + lane) * 16], wal, 16);
+        for (int q = 0; q < 4; ++q) memcpy(&img[((2 + q) * 64 + lane) * 16], b + 16 * kg + 4 * q, 16);
+    }
+    return img;
+}
+
 template <typename E>
 static inline std::vector<uint8_t> as_bytes(const std::vector<E>& v) {
     std::vector<uint8_t> b(v.size() * sizeof(E));

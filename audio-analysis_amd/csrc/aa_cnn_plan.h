@@ -46,6 +46,7 @@ struct Stage {
     // packed weights (empty: pool_dense without a Dense reads a null pointer),
     // bias [+ fp8 dequantisation scales], the fused tail's head weights
     std::vector<uint8_t> h_w, h_tw;
+    std::vector<uint8_t> h_f1;  // split-bf16 fused_first: the first conv's per-lane image (pack_first_lanes)
     std::vector<float> h_b;
     int layer_end = 0;  // index of the first layer after this stage's group
     void* d_w = nullptr;
@@ -62,6 +63,7 @@ struct Stage {
     int wg_npass = 1;     // its staging passes (planes per pass = (wg + 2) / wg_npass)
     int cin_pad = 0;      // ST_GCONV: C_in rounded up to 32
     int tail = 0;         // ST_HEAD, split-bf16: computes the previous conv stage itself (aa_conv_tail.h)
+    void* d_f1 = nullptr;
     void* d_tw = nullptr;  // tail: head weights packed per wave / label fragment, hi then lo
     int pair = 0;         // split-bf16: a full forward computes the previous stage inside this one (aa_conv_pair.h)
 };
@@ -334,6 +336,12 @@ static void fuse_first_conv(std::vector<Stage>& st, int prec) {
     const double es1 = (double)prec_bytes(prec);
     st[1].bytes = 4.0 * st[0].Hin * st[0].Win * st[0].cin + (st[1].bytes - es1 * st[1].Hin * st[1].Win * st[1].cin);
     st[1].name = st[0].name + "+" + st[1].name;
+    // (the skipped first conv keeps its f32 images: [32][9] weights, 32 biases)
+    if (prec == AA_PREC_BF16X3) {
+        std::vector<float> w1(32 * 9);
+        memcpy(w1.data(), st[0].h_w.data(), w1.size() * sizeof(float));
+        st[1].h_f1 = pack_first_lanes(w1.data(), st[0].h_b.data());
+    }
 }
 
 // split-bf16: a conv_x3 stage whose consumer is another conv_x3 stage

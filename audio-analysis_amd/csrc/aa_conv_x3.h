@@ -82,7 +82,11 @@ constexpr int x3_waves_per_simd() {
     return w < 1 ? 1 : (w > 8 ? 8 : w);
 }
 
-// Two f32 values as packed bf16 hi and lo words (5 VALU ops)
+// Two f32 values as packed bf16 hi and lo words (5 VALU ops).  The 2-vector
+// subtract stays one v_pk_add_f32 under -fno-slp-vectorize; as two scalar
+// subtracts (leaky_split2's form) the Winograd 9x3 kernel, whose staging
+// holds 32 of them per wave and is not issue-bound, measured 1 % slower in
+// both trace orders (profiles/r11/fused_first.txt)
 __device__ __forceinline__ void split2(float x0, float x1, uint32_t& hi, uint32_t& lo) {
     typedef __attribute__((ext_vector_type(2))) float f2;
     typedef __attribute__((ext_vector_type(2))) __bf16 b2;
@@ -93,10 +97,13 @@ __device__ __forceinline__ void split2(float x0, float x1, uint32_t& hi, uint32_
 }
 
 // Two activations max(x, a x) (0 <= a <= 1) as packed bf16 hi and lo
-// words, in 8 VALU ops: two multiplies, two raw maxes, one packed conversion
+// words, in 10 VALU ops: two multiplies, two raw maxes, one packed conversion
 // for hi, its two halves back to f32 (shift / mask), two subtracts, one
-// packed conversion for lo.  The max is v_med3_f32(x, a x, +inf) through the
-// builtin: max(x, a x) for every non-NaN x (the inputs are MFMA results),
+// packed conversion for lo (tools/isa_count.py: no same-source v_max_f32 in
+// the fused kernel's first-layer phase).  The max is v_med3_f32(x, a x, +inf)
+// through the builtin: max(x, a x) for every non-NaN x (the inputs are MFMA
+// results; a x = NaN, from a = 0 and x = +-inf, still gives x: med3 with a NaN
+// operand returns the minimum of the other two, and the third is +inf),
 // without the NaN canonicalisation a plain fmaxf adds, and -- unlike an
 // inline-asm v_max_f32 -- visible to the hazard recognizer, which pads the
 // first VALU read of an MFMA result with the wait states the matrix pipe
@@ -104,10 +111,16 @@ __device__ __forceinline__ void split2(float x0, float x1, uint32_t& hi, uint32_
 __device__ __forceinline__ void leaky_split2(float x0, float x1, float a, uint32_t& hi, uint32_t& lo) {
     typedef __attribute__((ext_vector_type(2))) float f2;
     typedef __attribute__((ext_vector_type(2))) __bf16 b2;
-    constexpr float inf = __builtin_inff();
+    // +inf as a scalar register the optimiser cannot see through: with the
+    // literal it folds med3(x, r, +inf) to maxnum(x, r), whose lowering
+    // canonicalises x first (v_max_f32 x, x, x: one more VALU op per value).
+    // The asm has no inputs and is not volatile: a scalar move or three per
+    // kernel, no vector issue.
+    float top;
+    asm("s_mov_b32 %0, 0x7f800000" : "=s"(top));
     const float r0 = x0 * a, r1 = x1 * a;
-    const float o0 = __builtin_amdgcn_fmed3f(x0, r0, inf);
-    const float o1 = __builtin_amdgcn_fmed3f(x1, r1, inf);
+    const float o0 = __builtin_amdgcn_fmed3f(x0, r0, top);
+    const float o1 = __builtin_amdgcn_fmed3f(x1, r1, top);
     hi = __builtin_bit_cast(uint32_t, __builtin_convertvector(f2{o0, o1}, b2));
     // (scalar subtracts: aa_cnn.hip is built with -fno-slp-vectorize, which
     // keeps them from being packed into v_pk_add_f32 -- an expensive issue
@@ -372,9 +385,11 @@ __device__ __forceinline__ void x3_store(const float* E, const float* __restrict
 // AJIT: A fragments read just in time inside the step (fewer VGPRs) instead
 // of a whole next-step set prefetched; OCC > 0 pins the waves per SIMD the
 // compiler must fit (its VGPR budget), 0 leaves it free up to the LDS limit.
+// LM (FUSED): the log-mel input's form, bit 0 float16 storage, bit 1 the
+// MagTransform power applied as it is staged.
 template <int KH, int KW, int CIN, int WM, int WN, int MF, int NF, int POOL, int TH, int TW, bool FUSED = false,
           int DIAG = 0, bool RING = true, bool AJIT = false, int OCC = 0, bool IN_SPLIT = false,
-          bool OUT_SPLIT = false>
+          bool OUT_SPLIT = false, int LM = 0>
 __global__ __launch_bounds__(WM * WN * 64)
 __attribute__((amdgpu_waves_per_eu(OCC ? OCC : 1,
                                     OCC ? OCC : x3_waves_per_simd<KH, KW, CIN, WM, WN, NF, TH, TW, FUSED, RING>())))
@@ -572,22 +587,22 @@ void conv_x3(const float* __restrict__ in, int Hin, int Win, const bf16* __restr
     bf16x8 f1_wa{}, f1_wal{};
     f32x16 f1_cb{};  // D register r: channel 16 kg + r
     if constexpr (FUSED) {
-        const int l32 = lane & 31, kg = lane >> 5;
-        const int ch1 = 16 * ((l32 >> 2) & 1) + 4 * (l32 >> 3) + (l32 & 3);
         // the 27 products of a pixel (hi.hi, hi.lo, lo.hi over 9 taps) in the
         // 32 k-slots of two MFMAs: MFMA 1 = wh.xh (k-group 0) and wh.xl
         // (k-group 1) over taps 0-7; MFMA 2 = wl.xh over taps 0-7 (k-group
         // 0) and wh8.xh8, wh8.xl8, wl8.xh8 (k-group 1)
-        float w9[9];
+        // Both operands and the bias depend on the model and the lane alone:
+        // the host builds them once (aa_cnn_pack.h pack_first_lanes, the
+        // split rounded as bf_hi / bf_lo round), [part][lane][16 B]
+        const uint4* img = reinterpret_cast<const uint4*>(fc.img) + lane;
+        f1_wa = __builtin_bit_cast(bf16x8, img[0]);
+        f1_wal = __builtin_bit_cast(bf16x8, img[64]);
 #pragma unroll
-        for (int t = 0; t < 9; ++t) w9[t] = fc.w[ch1 * 9 + t];
+        for (int qd = 0; qd < 4; ++qd) {
+            const f32x4 b4 = __builtin_bit_cast(f32x4, img[(2 + qd) * 64]);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            f1_wa[j] = bf_hi(w9[j]);
-            f1_wal[j] = kg == 0 ? bf_lo(w9[j]) : j < 2 ? bf_hi(w9[8]) : j == 2 ? bf_lo(w9[8]) : (bf16)0.f;
+            for (int r = 0; r < 4; ++r) f1_cb[4 * qd + r] = b4[r];
         }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) f1_cb[r] = fc.b[16 * kg + r];
     }
 
     if constexpr (!RING) read_b(F0, 0);  // its latency hides behind the first staging
@@ -670,7 +685,12 @@ void conv_x3(const float* __restrict__ in, int Hin, int Win, const bf16* __restr
             uint32_t* Xs = reinterpret_cast<uint32_t*>(smem + (size_t)PH * PW * 128);
             // buffer loads: the resource based at the window (64-bit, so any
             // batch size), the element in the lane's offset
-            const int esz = fc.lm_f16 ? 2 : 4;
+            // LM_F16 / LM_MAG are the instantiation's (launch_x3 picks it from
+            // fc.lm_f16 / fc.has_mag): no per-element branch between a pass's
+            // loads, which all issue before the one wait, and no powf body in
+            // the kernel of a model without MagTransform
+            constexpr bool LM_F16 = (LM & 1) != 0, LM_MAG = (LM & 2) != 0;
+            constexpr int esz = LM_F16 ? 2 : 4;
             const __amdgpu_buffer_rsrc_t lrs =
                 x3_wrsrc(reinterpret_cast<const char*>(in) + (size_t)n * fc.H0 * fc.W0 * esz);
             constexpr int lbase = 0;
@@ -678,15 +698,20 @@ void conv_x3(const float* __restrict__ in, int Hin, int Win, const bf16* __restr
             // pass of 2 over 256 threads), split in pairs
             constexpr int XU = (XN + NTHR - 1) / NTHR <= 2 ? 2 : 4;
             for (int i0 = 0; i0 < ((DIAG & 512) ? 0 : XN); i0 += XU * NTHR) {
-                float v[XU];
+                uint32_t raw[XU];
 #pragma unroll
                 for (int u = 0; u < XU; ++u) {
                     const int idx = min(i0 + u * NTHR + (int)threadIdx.x, XN - 1);
                     const int r = idx / XW, c = idx - r * XW;
                     const int e = min(oh0 + r, fc.H0 - 1) * fc.W0 + min(ow0 + c, fc.W0 - 1);
-                    v[u] = fc.lm_f16 ? (float)__builtin_bit_cast(_Float16, __builtin_amdgcn_raw_buffer_load_b16(lrs, e * 2, lbase, 0))
-                                     : __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(lrs, e * 4, lbase, 0));
-                    if (fc.has_mag) v[u] = powf(v[u], fc.mag_exp);
+                    if constexpr (LM_F16) raw[u] = __builtin_amdgcn_raw_buffer_load_b16(lrs, e * 2, lbase, 0);
+                    else raw[u] = __builtin_amdgcn_raw_buffer_load_b32(lrs, e * 4, lbase, 0);
+                }
+                float v[XU];
+#pragma unroll
+                for (int u = 0; u < XU; ++u) {
+                    v[u] = LM_F16 ? (float)__builtin_bit_cast(_Float16, (uint16_t)raw[u]) : __builtin_bit_cast(float, raw[u]);
+                    if constexpr (LM_MAG) v[u] = powf(v[u], fc.mag_exp);
                 }
 #pragma unroll
                 for (int u = 0; u < XU; u += 2) {

@@ -211,10 +211,15 @@ int aa_model_forward_prefix(void* model, const void* x, int32_t n, int32_t stage
  * weights (len 0 unless the stage is the fused tail).  *len: the image's
  * bytes; buf NULL: size query; AA_ERR_INVALID when cap < *len.  Planned
  * models only: a created model has released its host images
- * (AA_ERR_UNSUPPORTED). */
+ * (AA_ERR_UNSUPPORTED).
+ * first_lane_image, same contract: the split-bf16 fused first conv's per-lane
+ * image (6 parts x 64 lanes x 16 B: the lane's two MFMA weight operands as
+ * bf16, then its 16 bias values), uploaded with stage 1's weights; len 0 when
+ * the model has no such stage. */
 int aa_model_plan(const aa_layer* layers, int32_t n_layers, const float* blob, int64_t blob_len,
                   int32_t in_h, int32_t in_w, int32_t in_c, int32_t precision, void** model);
 int aa_model_stage_image(const void* model, int32_t stage, int32_t which, void* buf, size_t cap, size_t* len);
+int aa_model_first_lane_image(const void* model, void* buf, size_t cap, size_t* len);
 
 /* ---------------- CNN graphs (DAG models: residual / squeeze-excite / depthwise) ---------------- */
 /* Models that are not a single conv chain -- Keras Functional graphs such as

@@ -108,6 +108,13 @@ int main(int argc, char** argv) {
     (void)hipMemcpy(w1, hw1.data(), hw1.size() * 4, hipMemcpyHostToDevice);
     (void)hipMemcpy(b1, hb1.data(), hb1.size() * 4, hipMemcpyHostToDevice);
     FirstConv f1{w1, b1, 1, 0.3f, 0, 1.f, 160, 226};
+    {  // conv_x3 reads the first layer's weights and bias as the per-lane image
+        const std::vector<uint8_t> li = pack_first_lanes(hw1.data(), hb1.data());
+        void* dli;
+        (void)hipMalloc(&dli, li.size());
+        (void)hipMemcpy(dli, li.data(), li.size(), hipMemcpyHostToDevice);
+        f1.img = dli;
+    }
     const int which = argc > 1 ? atoi(argv[1]) : 0;  // 0: all layers, 9: ablations
     if (which == 9) {
         // DIAG bits (aa_cnn.hip): 1 no staging, 4 no stores, 32 no weight stream,
@@ -487,6 +494,39 @@ int main(int argc, char** argv) {
     }
     if (which == 21) {  // the shipped fused kernel, three timings (variant A/B across builds)
         FS(0) FS(0) FS(0)
+        return 0;
+    }
+    if (which == 23) {
+        // the shipped fused kernel's output words on seeded first-layer weights of both signs:
+        // written to argv[2]; compared word for word with argv[3] (the file another build wrote) when given
+        if (argc < 3) { printf("usage: conv_bench_x3 23 OUT.bin [OTHER.bin]\n"); return 2; }
+        srand(23);
+        for (auto& x : hw1) x = (rand() & 0xffff) / 65536.f - 0.5f;
+        for (auto& x : hb1) x = 0.2f * ((rand() & 0xffff) / 65536.f - 0.5f);
+        (void)hipMemcpy(w1, hw1.data(), hw1.size() * 4, hipMemcpyHostToDevice);
+        (void)hipMemcpy(b1, hb1.data(), hb1.size() * 4, hipMemcpyHostToDevice);
+        const std::vector<uint8_t> li = pack_first_lanes(hw1.data(), hb1.data());
+        (void)hipMemcpy(const_cast<void*>(f1.img), li.data(), li.size(), hipMemcpyHostToDevice);
+        const size_t words = (size_t)n * 52 * 74 * 32;  // pooled 156 x 222 -> 52 x 74, 32 channels, 4 B each (grouped split)
+        (void)hipMemset(out, 0, words * 4);
+        time_one<3, 3, 32, 4, 1, 4, 2, 3, 12, 21, true, 0, false, true, 0, false, true>("c1+c2", n, 158, 224, 32, in, w, b, out, f1, 1);
+        std::vector<uint32_t> o(words), other(words);
+        (void)hipMemcpy(o.data(), out, words * 4, hipMemcpyDeviceToHost);
+        FILE* f = fopen(argv[2], "wb");
+        if (!f || fwrite(o.data(), 4, words, f) != words) { printf("cannot write %s\n", argv[2]); return 2; }
+        fclose(f);
+        size_t nz = 0;
+        for (uint32_t x : o) nz += x != 0;
+        printf("fused stage: %zu output words (%zu nonzero) -> %s\n", words, nz, argv[2]);
+        if (argc > 3) {
+            f = fopen(argv[3], "rb");
+            if (!f || fread(other.data(), 4, words, f) != words) { printf("cannot read %s\n", argv[3]); return 2; }
+            fclose(f);
+            size_t nd = 0;
+            for (size_t i = 0; i < words; ++i) nd += o[i] != other[i];
+            printf("fused stage: %zu of %zu output words differ from %s\n", nd, words, argv[3]);
+            return nd ? 1 : 0;
+        }
         return 0;
     }
     if (which == 22) {  // per-wave phase timestamps of the shipped fused kernel -> gpurun_out/fused_ts.bin
