@@ -12,20 +12,16 @@ K at a time:
   * decode: worker threads read each PCM16 48 kHz WAV straight into a pinned
     host slot (other formats and rates go through ``load_recording``); the
     batch crosses PCIe as int16 and ``aa_pcm_s16_to_f32`` widens it on the
-    device exactly as the host decode would.  With ``flac="gpu"`` a FLAC
-    file stays compressed in its slot too: the worker only indexes its frames
-    (``flac_gpu.index``), the compressed bytes cross PCIe, and one
-    ``aa_flac_decode_device`` per batch decodes them into the same int16
-    staging buffer; a file with a frame the device does not vouch for is
-    redone through ``load_recording``, so its samples or its failure are the
-    host route's.  With ``vorbis="gpu"`` an Ogg Vorbis file goes the same way:
-    the worker indexes it (``vorbis_gpu.index``: packets, block timeline,
-    flattened setup), the packet bytes cross PCIe, and one
-    ``aa_vorbis_decode_device`` per batch decodes them into the staging buffer.
-    With ``mp3="gpu"`` an MP3 file likewise: the worker indexes it
-    (``mp3_gpu.index``: headers, side info, the bit reservoir laid out flat),
-    the main data cross PCIe, and one ``aa_mp3_decode_device`` per batch
-    decodes them -- with the host decoder's own core, so no file is redone;
+    device exactly as the host decode would.  A FLAC, Ogg Vorbis or MP3 file
+    whose mode is "gpu" (``CODECS``: ``flac=``, ``vorbis=``, ``mp3=``) stays
+    compressed in its slot too: the worker only indexes it (the codec module's
+    ``index_slot``: FLAC frames; Vorbis packets, block timeline and flattened
+    setup; MP3 headers, side info and the bit reservoir laid out flat), the
+    compressed bytes cross PCIe, and the module's ``decode_batch`` decodes
+    every such file of the batch into the same int16 staging buffer.  A file
+    the device does not vouch for is redone through ``load_recording``, so
+    its samples or its failure are the host route's (MP3 runs the host
+    decoder's own core on the device, so none of its files is redone);
   * get_end: one ``aa_span_nonzero`` launch over every file's chunk spans,
     one readback;
   * signal_noise: ``aa_sn_run_batch`` -- per file the STFT / medians / mask
@@ -51,13 +47,22 @@ import struct
 import time
 from concurrent.futures import ThreadPoolExecutor
 from dataclasses import dataclass, field
+from functools import partial
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, flac_gpu, mp3_gpu, vorbis_gpu
+from .resample import out_length
 
 SR = 48000
+# The device codecs (see _codec), in the order decode_into tries them and a batch
+# launches them: name (the keyword argument), module, environment variable, default
+# mode.  FLAC is "gpu" by the corpus A/B of DESIGN section 4 (`flac_decode_frames`);
+# Vorbis and MP3 are opt-in until theirs say otherwise (`vorbis_unpack`, `mp3_unpack`).
+CODECS = (("flac", flac_gpu, "AA_FLAC", "gpu"),
+          ("vorbis", vorbis_gpu, "AA_VORBIS", "host"),
+          ("mp3", mp3_gpu, "AA_MP3", "host"))
 
 
 @dataclass
@@ -76,23 +81,17 @@ class Decoded:
     sr_in: int = SR
     slot: int = -1
     dev: object = None       # the recording's samples in the batch's device PCM
-    flac: object = None      # flac="gpu": the frame table (flac_gpu.FRAME) of the compressed bytes ...
-    comp_t: object = None    # ... which are this pinned torch uint8 view of the slot
-    vorbis: object = None    # vorbis="gpu": the index (vorbis_gpu.Indexed); comp_t: its packet bytes in the slot
-    mp3: object = None       # mp3="gpu": the index (mp3_gpu.Indexed); comp_t: its flat main data in the slot
-    n_in: int = 0            # frames at sr_in the table decodes to
+    codec: object = None     # decoded on the device: the module of CODECS that does it, ...
+    index: object = None     # ... its index of the file (Slotted.index: flac_gpu.FRAME table, vorbis_gpu / mp3_gpu Indexed) ...
+    comp_t: object = None    # ... and the compressed bytes: this pinned torch uint8 view of the slot, ...
+    nbytes: int = 0          # ... this many
+    n_in: int = 0            # frames at sr_in the index decodes to
     path: str = ""
 
     def frames(self):
         """Host float32 samples at 48 kHz (only band-pass filtered tracks need them)."""
-        if self.f32 is None and self.flac is not None:  # decoded on the device: the host decode, lazily
-            from .audio import _to_mono, decode_flac
-            q, ch, _ = decode_flac(self.comp_t.numpy().tobytes())
-            self.f32 = _to_mono(q, ch)
-        if self.f32 is None and (self.vorbis is not None or self.mp3 is not None):
-            # (the slot holds packets / main data, not the file: read it again)
-            from .audio import decode
-            self.f32 = decode(self.path)[0]
+        if self.f32 is None and self.codec is not None:  # decoded on the device: the host decode, lazily
+            self.f32 = self.codec.host_samples(self)
         if self.f32 is None:
             from .audio import _to_mono
             self.f32 = _to_mono(np.asarray(self.s16), self.channels)
@@ -161,43 +160,27 @@ class SlotPool:
             self._cv.notify()
 
 
-def flac_mode(flac=None) -> str:
-    """"host" (aa_flac_decode on a decoder thread) or "gpu" (aa_flac_decode_device
-    per batch); None: AA_FLAC, else "gpu" -- the default by the corpus A/B of
-    DESIGN section 4 (`flac_decode_frames`)."""
-    mode = flac or os.environ.get("AA_FLAC") or "gpu"
+def codec_mode(name, value=None) -> str:
+    """How the corpus path decodes the files of codec ``name`` of CODECS: "host"
+    (on a decoder thread) or "gpu" (on the device, per batch); None: the
+    codec's environment variable, else its default."""
+    env, default = next(c[2:] for c in CODECS if c[0] == name)
+    mode = value or os.environ.get(env) or default
     if mode not in ("host", "gpu"):
-        raise ValueError(f"flac={mode!r}: \"host\" or \"gpu\"")
+        raise ValueError(f"{name}={mode!r}: \"host\" or \"gpu\"")
     return mode
 
 
-def vorbis_mode(vorbis=None) -> str:
-    """"host" (aa_vorbis_decode on a decoder thread) or "gpu"
-    (aa_vorbis_decode_device per batch); None: AA_VORBIS, else "host" -- opt-in
-    until the corpus A/B of DESIGN section 4 (`vorbis_unpack`) says otherwise."""
-    mode = vorbis or os.environ.get("AA_VORBIS") or "host"
-    if mode not in ("host", "gpu"):
-        raise ValueError(f"vorbis={mode!r}: \"host\" or \"gpu\"")
-    return mode
+flac_mode = partial(codec_mode, "flac")
+vorbis_mode = partial(codec_mode, "vorbis")
+mp3_mode = partial(codec_mode, "mp3")
 
 
-def mp3_mode(mp3=None) -> str:
-    """"host" (aa_mp3_decode on a decoder thread) or "gpu" (aa_mp3_decode_device
-    per batch); None: AA_MP3, else "host" -- opt-in until a corpus A/B on the
-    device says otherwise (`mp3_unpack`)."""
-    mode = mp3 or os.environ.get("AA_MP3") or "host"
-    if mode not in ("host", "gpu"):
-        raise ValueError(f"mp3={mode!r}: \"host\" or \"gpu\"")
-    return mode
-
-
-def decode_into(path, pool: SlotPool, flac="host", vorbis="host", mp3="host",  # (BatchAnalyser passes its modes)
-                sr_out=SR, wav_any_rate=False, host_decode=None):
+def decode_into(path, pool: SlotPool, codecs=(), sr_out=SR, wav_any_rate=False, host_decode=None):
     """Decode one file; PCM16 48 kHz WAV lands in a pinned slot untouched, and
-    with flac="gpu" an indexable FLAC file stays there compressed; with
-    vorbis="gpu" an indexable Ogg Vorbis file stays there as its audio packets
-    (the index writes them over the file's bytes), and with mp3="gpu" an MP3
-    file as its flat main data (likewise).
+    a file that one of ``codecs`` (modules of CODECS) takes stays there compressed: a
+    FLAC file as it is, an Ogg Vorbis file as its audio packets and an MP3 file
+    as its flat main data (the index writes them over the file's bytes).
     The file comes in with one aa_read_file call (stat, open, read, close
     without the interpreter lock: the decoder threads otherwise queued for it
     behind the lanes' Python at every step).
@@ -207,7 +190,6 @@ def decode_into(path, pool: SlotPool, flac="host", vorbis="host", mp3="host",  #
     (path -> (mono f32, rate); default load_recording at the file's rate)."""
     import ctypes as C
     from . import identify_tracks as it
-    from .audio import _is_flac
     i = pool.get()
     got = C.c_int64(0)
     rc = _lib.lib().aa_read_file(os.fsencode(path), pool.t[i].data_ptr(), pool.bytes, C.byref(got))
@@ -222,49 +204,21 @@ def decode_into(path, pool: SlotPool, flac="host", vorbis="host", mp3="host",  #
                 off, nb, ch, sr = w
                 t = pool.t[i][off:off + nb].view(torch.int16)
                 n_in = nb // (2 * ch)
-                n = n_in
-                if sr != sr_out:
-                    from .resample import out_length
-                    n = out_length(n_in, sr, sr_out)
+                n = n_in if sr == sr_out else out_length(n_in, sr, sr_out)
                 return Decoded(n=n, sr=sr_out, s16=buf[off:off + nb].view(np.int16), s16_t=t,
                                channels=ch, sr_in=sr, slot=i, n_in=n_in, path=str(path))
-            if flac == "gpu" and _is_flac(buf, got.value):
-                from . import flac_gpu
-                from .resample import out_length
-                ix = flac_gpu.index(buf[:got.value])
-                if ix is not None and ix[0].total_frames > 0 and flac_gpu.fits_batch(ix[1]):
-                    info, tab = ix
-                    return Decoded(n=out_length(info.total_frames, info.sample_rate, sr_out), sr=sr_out,
-                                   channels=info.channels, sr_in=info.sample_rate, slot=i, flac=tab,
-                                   comp_t=pool.t[i][:got.value], n_in=info.total_frames, path=str(path))
-            if vorbis == "gpu" and got.value >= 4 and bytes(buf[:4]) == b"OggS":
-                from . import vorbis_gpu
-                from .resample import out_length
-                ix = vorbis_gpu.index(buf[:got.value], payload=buf)
-                if ix is not None and int(ix.stream["frames"][0]) > 0 and vorbis_gpu.fits_batch(ix):
-                    st = ix.stream[0]
-                    n_in, sr_in = int(st["frames"]), int(st["sample_rate"])
-                    return Decoded(n=out_length(n_in, sr_in, sr_out), sr=sr_out, channels=int(st["channels"]), sr_in=sr_in,
-                                   slot=i, vorbis=ix, comp_t=pool.t[i][:ix.payload.size], n_in=n_in, path=str(path))
-            if mp3 == "gpu":
-                from .audio import _is_mp3
-                if _is_mp3(buf, got.value):
-                    from . import mp3_gpu
-                    from .resample import out_length
-                    ix = mp3_gpu.index(buf[:got.value], payload=buf)
-                    if ix is not None and int(ix.stream["frames"][0]) > 0 and mp3_gpu.fits_batch(ix):
-                        st = ix.stream[0]
-                        n_in, sr_in = int(st["frames"]), int(st["sample_rate"])
-                        return Decoded(n=out_length(n_in, sr_in, sr_out), sr=sr_out, channels=int(st["channels"]),
-                                       sr_in=sr_in, slot=i, mp3=ix, comp_t=pool.t[i][:ix.payload.size], n_in=n_in,
-                                       path=str(path))
+            for codec in codecs:
+                s = codec.index_slot(buf, got.value) if codec.sniff(buf, got.value) else None
+                if s is not None:
+                    return Decoded(n=out_length(s.n_in, s.sr_in, sr_out), sr=sr_out, channels=s.channels,
+                                   sr_in=s.sr_in, slot=i, codec=codec, index=s.index, nbytes=s.payload_bytes,
+                                   comp_t=pool.t[i][:s.payload_bytes], n_in=s.n_in, path=str(path))
         except Exception:
             pool.put(i)
             raise
     pool.put(i)  # (larger than a slot, or not a 48 kHz PCM16 WAV)
     # FLAC, other WAV encodings; other rates are resampled on the device at upload
     frames, sr = host_decode(str(path)) if host_decode else it.load_recording(str(path), resample=None)
-    from .resample import out_length
     return Decoded(n=out_length(len(frames), sr, sr_out), sr=sr_out,
                    f32=np.ascontiguousarray(frames, dtype=np.float32), sr_in=sr, n_in=len(frames), path=str(path))
 
@@ -313,6 +267,47 @@ class _Rec:
     err: object = None
 
 
+def split_items(items):
+    """items of process(): (_Rec of every decoded file, _Rec with ``err`` of every file whose decode raised)."""
+    recs, failed = [], []
+    for idx, path, dec, meta in items:
+        if isinstance(dec, BaseException):
+            failed.append(_Rec(idx, str(path), None, meta, err=dec))
+        else:
+            recs.append(_Rec(idx, str(path), dec, meta))
+    return recs, failed
+
+
+def return_slots(pool, recs):
+    if pool is not None:
+        for r in recs:
+            if r.dec.slot >= 0:
+                pool.put(r.dec.slot)
+                r.dec.slot = -1
+
+
+def staging_layout(decs):
+    """Where a batch's recordings go, from the Decodeds alone: per recording
+    (off, o16, oc) -- its first sample in the batch's f32 PCM (``n`` each, back
+    to back), its first element in the int16 staging buffer (PCM16 as it is; a
+    compressed file the n_in * channels samples it decodes to; None: host f32)
+    and its first byte in the compressed buffer (None: not compressed) -- and
+    the three buffers' sizes."""
+    places, off, o16, oc = [], 0, 0, 0
+    for d in decs:
+        if d.codec is not None:
+            places.append((off, o16, oc))
+            oc += d.nbytes
+            o16 += d.n_in * d.channels
+        elif d.s16 is not None:
+            places.append((off, o16, None))
+            o16 += d.s16.size
+        else:
+            places.append((off, None, None))
+        off += d.n
+    return places, off, o16, oc
+
+
 class _Lane:
     """One batch in flight: its own HIP stream and every device buffer a batch
     touches (PCM, int16 staging, signal_noise workspace and result slots, the
@@ -329,13 +324,14 @@ class _Lane:
         self.sn_ws = None
         self.sn_buf = None
         self.ws = {}  # classify_batch workspaces
-        # flac="gpu" / vorbis="gpu": compressed bytes, decode workspace, per-frame status, f32 before a resample
-        self.flac = {}
+        # grow-only buffers by purpose: compressed bytes, the codecs' workspaces and
+        # (shared) status, f32 before a resample, the old index's segments and workspace
+        self._scratch = {}
 
-    def flac_buffer(self, name, n, dtype):
-        t = self.flac.get(name)
+    def scratch(self, name, n, dtype):
+        t = self._scratch.get(name)
         if t is None or t.numel() < n:
-            t = self.flac[name] = torch.empty(int(n * 1.25) + 1, dtype=dtype, device=self.dev)
+            t = self._scratch[name] = torch.empty(int(n * 1.25) + 1, dtype=dtype, device=self.dev)
         return t
 
     def buffers(self, n_f32, n_s16):
@@ -347,8 +343,6 @@ class _Lane:
 
 
 SN_CAP = 4096   # components per recording kept in the batch slots
-VORBIS_WS_BYTES = 1 << 30  # workspace one aa_vorbis_decode_device call of a batch may take
-MP3_WS_BYTES = 1 << 30     # the same for aa_mp3_decode_device (sixteen 60 s clips need about 0.86 GB)
 PREFETCH = 2    # batches decoded ahead of the newest batch a lane has taken
 _SN_LOCK = __import__("threading").Lock()
 SN_HEAD = 64    # component rows read back with the counts (more: a second copy)
@@ -373,178 +367,108 @@ class BatchAnalyser:
 
     def __init__(self, bird_models, analyse_tracks=False, device=None, precision=None, batch=16, workers=8,
                  lanes=2, flac=None, vorbis=None, mp3=None):
-        """flac: "host" decodes FLAC files on the decoder threads (aa_flac_decode),
-        "gpu" on the device per batch (aa_flac_decode_device); None: AA_FLAC, else "gpu".
-        vorbis: the same for Ogg Vorbis files (aa_vorbis_decode / aa_vorbis_decode_device);
-        None: AA_VORBIS, else "host".
-        mp3: the same for MP3 files (aa_mp3_decode / aa_mp3_decode_device); None: AA_MP3, else "host"."""
-        self.flac = flac_mode(flac)
-        self.vorbis = vorbis_mode(vorbis)
-        self.mp3 = mp3_mode(mp3)
+        """flac, vorbis, mp3: "host" decodes such files on the decoder threads, "gpu"
+        on the device per batch; None: AA_FLAC / AA_VORBIS / AA_MP3, else the default (codec_mode)."""
         from .identify_tracks import _group_models
         from .pipeline import Classifier
+        self._setup(device, batch, workers, lanes, flac, vorbis, mp3)
         self.bird_models = bird_models
         self.analyse_tracks = bool(analyse_tracks)
+        self.groups = _group_models(bird_models) if bird_models is not None else None
+        self.clf = Classifier.shared(precision=precision, device=self.dev)
+
+    def _setup(self, device, batch, workers, lanes, flac, vorbis, mp3):
+        """What the run loop and the staging of a batch need (CiBatchAnalyser's too)."""
+        given = {"flac": flac, "vorbis": vorbis, "mp3": mp3}
+        self.codecs = [mod for name, mod, _, _ in CODECS if codec_mode(name, given[name]) == "gpu"]  # for decode_into
         self.dev = torch.device(device or "cuda")
         self.K = int(batch)
         self.workers = int(workers)
         self.n_lanes = max(1, int(lanes))
-        self.groups = _group_models(bird_models) if bird_models is not None else None
-        self.clf = Classifier.shared(precision=precision, device=self.dev)
         self.timing = _Laps()
 
     # ---- one batch --------------------------------------------------------
+    def _stage(self, lane, recs, f32=True):
+        """The batch's slots into the lane's buffers on lane.copy, each recording
+        where staging_layout puts it (r.off, r.dec.o16, r.dec.oc): compressed
+        bytes into comp, PCM16 into s16 and, with ``f32``, host-decoded samples
+        already at 48 kHz into pcm.  Returns (pcm, s16, comp, total, cur)."""
+        places, total, n16, nc = staging_layout([r.dec for r in recs])
+        pcm, s16 = lane.buffers(total if f32 else 0, n16)
+        comp = lane.scratch("bytes", nc, torch.uint8) if any(r.dec.codec is not None for r in recs) else None
+        cur = torch.cuda.current_stream(self.dev)
+        lane.copy.wait_stream(cur)  # the lane's previous batch is done with the buffers
+        with torch.cuda.stream(lane.copy):
+            for r, (off, o16, oc) in zip(recs, places):
+                d = r.dec
+                r.off, d.o16, d.oc = off, o16, oc
+                if d.codec is not None:  # compressed; decoded into s16[o16:] by _decode_compressed
+                    comp[oc:oc + d.nbytes].copy_(d.comp_t, non_blocking=True)
+                elif d.s16 is not None:
+                    s16[o16:o16 + d.s16.size].copy_(d.s16_t, non_blocking=True)
+                elif f32 and d.sr_in == SR:
+                    pcm[off:off + d.n].copy_(torch.from_numpy(d.f32), non_blocking=False)
+        cur.wait_stream(lane.copy)
+        return pcm, s16, comp, total, cur
+
+    def _decode_compressed(self, lane, recs, comp, s16, cur, pcm=None, total=0):
+        """Each codec's decode_batch, in CODECS order, over its files of the
+        batch (compressed bytes in comp, samples into s16); the files a codec
+        does not vouch for are redone on the host (_redo_on_host) before the
+        next codec runs.  Returns (pcm, total) as _redo_on_host leaves them."""
+        for _, codec, _, _ in CODECS:
+            rs = [r for r in recs if r.dec.codec is codec]
+            if not rs:
+                continue
+            bad = codec.decode_batch(lane.scratch, [r.dec.index for r in rs], [r.dec.oc for r in rs],
+                                     [r.dec.o16 for r in rs], comp, s16, self.dev, cur)
+            if bad:
+                pcm, total = self._redo_on_host(lane, [rs[k] for k in bad], pcm, total)
+        return pcm, total
+
     def _upload(self, lane, recs):
         """PCM of the batch into one device f32 buffer (recording r at r.off)."""
-        total = sum(r.dec.n for r in recs)
-        n16 = sum(r.dec.n * r.dec.channels for r in recs if r.dec.s16 is not None)
-        fl = [r for r in recs if r.dec.flac is not None]
-        vb = [r for r in recs if r.dec.vorbis is not None]
-        m3 = [r for r in recs if r.dec.mp3 is not None]
-        n16 += sum(r.dec.n_in * r.dec.channels for r in fl + vb + m3)
-        pcm, s16 = lane.buffers(total, n16)
-        comp = (lane.flac_buffer("bytes", sum(r.dec.comp_t.numel() for r in fl + vb + m3), torch.uint8)
-                if fl or vb or m3 else None)
-        cur = torch.cuda.current_stream(self.dev)
-        lane.copy.wait_stream(cur)  # the lane's previous batch is done with both buffers
-        off = o16 = oc = 0
-        with torch.cuda.stream(lane.copy):
-            for r in recs:
-                r.off = off
-                d = r.dec
-                if d.flac is not None or d.vorbis is not None or d.mp3 is not None:  # compressed; decoded into s16[o16:] below
-                    comp[oc:oc + d.comp_t.numel()].copy_(d.comp_t, non_blocking=True)
-                    d.oc, d.o16 = oc, o16
-                    oc += d.comp_t.numel()
-                    o16 += d.n_in * d.channels
-                elif d.s16 is not None:
-                    s16[o16:o16 + d.s16_t.numel()].copy_(d.s16_t, non_blocking=True)
-                    d.o16 = o16
-                    o16 += d.s16_t.numel()
-                elif d.sr_in == SR:
-                    pcm[off:off + d.n].copy_(torch.from_numpy(d.f32), non_blocking=False)
-                off += d.n
-        cur.wait_stream(lane.copy)
+        pcm, s16, comp, total, cur = self._stage(lane, recs)
         L = _lib.lib()
         from .resample import resample_device
-        if fl:
-            pcm, total = self._flac_decode(lane, fl, comp, s16, pcm, total, cur)
-        if vb:
-            pcm, total = self._vorbis_decode(lane, vb, comp, s16, pcm, total, cur)
-        if m3:
-            self._mp3_decode(lane, m3, comp, s16, cur)
-        # every recording mono PCM16 (or FLAC decoded to it) at 48 kHz: the int16
-        # and f32 offsets coincide, so one widening launch covers the batch.  (A
-        # file that failed its host redo counts too: it still holds its place in
-        # both buffers, and only as mono 48 kHz are the two places the same.)
-        mono16 = all((r.dec.s16 is not None or
-                      ((r.dec.flac is not None or r.dec.vorbis is not None or r.dec.mp3 is not None) and
-                       r.dec.sr_in == SR)) and
+        pcm, total = self._decode_compressed(lane, recs, comp, s16, cur, pcm, total)
+        # every recording mono PCM16 (or a compressed file decoded to it) at 48 kHz:
+        # the int16 and f32 offsets coincide, so one widening launch covers the
+        # batch.  (A file that failed its host redo counts too: it still holds its
+        # place in both buffers, and only as mono 48 kHz are the two places the same.)
+        mono16 = all((r.dec.s16 is not None or (r.dec.codec is not None and r.dec.sr_in == SR)) and
                      r.dec.channels == 1 for r in recs)
-        if mono16 and total:
-            _lib.check(L.aa_pcm_s16_to_f32(_lib.dptr(s16), total, 1, _lib.dptr(pcm), _lib.stream_ptr(cur)),
+
+        def widen(o16, n, channels, dst):  # n frames from s16[o16:] as mono f32 to the device address dst
+            _lib.check(L.aa_pcm_s16_to_f32(_lib.dptr(s16) + 2 * o16, n, channels, dst, _lib.stream_ptr(cur)),
                        "aa_pcm_s16_to_f32")
+
+        if mono16 and total:
+            widen(0, total, 1, _lib.dptr(pcm))
         for r in recs:
             d = r.dec
             d.dev = pcm[r.off:r.off + d.n]
             if mono16 or r.err is not None:
                 continue
-            if d.flac is not None or d.vorbis is not None or d.mp3 is not None:
-                if d.sr_in == SR:
-                    _lib.check(L.aa_pcm_s16_to_f32(_lib.dptr(s16) + 2 * d.o16, d.n, d.channels,
-                                                   _lib.dptr(pcm) + 4 * r.off, _lib.stream_ptr(cur)),
-                               "aa_pcm_s16_to_f32")
-                else:  # widen at the file's rate, then librosa.resample to 48 kHz as the host route does
-                    tmp = lane.flac_buffer("f32", d.n_in, torch.float32)[:d.n_in]
-                    _lib.check(L.aa_pcm_s16_to_f32(_lib.dptr(s16) + 2 * d.o16, d.n_in, d.channels, _lib.dptr(tmp),
-                                                   _lib.stream_ptr(cur)), "aa_pcm_s16_to_f32")
-                    resample_device(tmp, d.sr_in, SR, out=d.dev)
-            elif d.s16 is not None and d.n:
-                _lib.check(L.aa_pcm_s16_to_f32(_lib.dptr(s16) + 2 * d.o16, d.n, d.channels,
-                                               _lib.dptr(pcm) + 4 * r.off, _lib.stream_ptr(cur)),
-                           "aa_pcm_s16_to_f32")
+            if d.codec is not None and d.sr_in != SR:
+                # widen at the file's rate, then librosa.resample to 48 kHz as the host route does
+                tmp = lane.scratch("f32", d.n_in, torch.float32)[:d.n_in]
+                widen(d.o16, d.n_in, d.channels, _lib.dptr(tmp))
+                resample_device(tmp, d.sr_in, SR, out=d.dev)
+            elif d.codec is not None or (d.s16 is not None and d.n):
+                widen(d.o16, d.n, d.channels, _lib.dptr(pcm) + 4 * r.off)
             elif d.s16 is None and d.sr_in != SR:  # librosa.resample to 48 kHz (aa_amd.resample)
                 resample_device(torch.from_numpy(d.f32).to(self.dev), d.sr_in, SR, out=d.dev)
         return pcm[:total]
 
-    def _flac_decode(self, lane, fl, comp, s16, pcm, total, cur):
-        """One aa_flac_decode_device over the batch's FLAC files (compressed
-        bytes in comp, samples into s16), then the per-frame statuses: a file
-        with any frame not OK is redone through load_recording, the host route,
-        whose samples -- or whose "Could not load" -- then stand for it.
-        Returns (pcm, total): the host route may decode another number of
-        samples than the index counted (a crafted stream); fewer use the head
-        of the file's place in pcm, more move the file behind the batch."""
-        from . import flac_gpu
-        tab = flac_gpu.concat([r.dec.flac for r in fl], [r.dec.oc for r in fl], [r.dec.o16 for r in fl])
-        status = lane.flac_buffer("status", len(tab), torch.int32)[:len(tab)]
-        ws = lane.flac_buffer("ws", max(flac_gpu.workspace_bytes(tab) // 4, 1), torch.int32)
-        flac_gpu.decode_device(comp, flac_gpu.table_to_device(tab, self.dev), len(tab), status, ws, out_s16=s16,
-                               stream=cur)
-        st = status.cpu().numpy()  # before any of these files' samples is used
-        bad = sorted(set(tab["stream"][st != _lib.AA_FLAC_OK].tolist()))
-        return self._redo_on_host(lane, [fl[k] for k in bad], pcm, total)
-
-    def _vorbis_decode(self, lane, vb, comp, s16, pcm, total, cur):
-        """aa_vorbis_decode_device over the batch's Ogg Vorbis files (packet
-        bytes in comp, samples into s16), then the per-packet statuses, read
-        before any sample is used: a file with any packet not OK is redone
-        through load_recording like a FLAC file (_flac_decode).  The files are
-        taken in as many calls as keep one call's workspace under
-        VORBIS_WS_BYTES (a file alone may exceed it)."""
-        from . import vorbis_gpu as vg
-        groups, size = [[]], 0
-        for r in vb:
-            need = vg.workspace_bytes(r.dec.vorbis.packets, r.dec.vorbis.stream)
-            if groups[-1] and size + need > VORBIS_WS_BYTES:
-                groups.append([])
-                size = 0
-            groups[-1].append(r)
-            size += need
-        bad = []
-        for g in groups:
-            b = vg.concat([r.dec.vorbis for r in g], [r.dec.oc for r in g], [r.dec.o16 for r in g])
-            if not len(b.packets):
-                continue
-            pl, nb = vg.plan(b.packets, b.streams)
-            status = lane.flac_buffer("status", len(b.packets), torch.int32)[:len(b.packets)]
-            ws = lane.flac_buffer("vorbis_ws", max(nb // 8, 1), torch.int64)
-            vg.decode_device(comp, vg.to_device(b.packets, self.dev), len(b.packets), vg.to_device(b.streams, self.dev),
-                             len(b.streams), vg.to_device(b.setups, self.dev), pl, status, ws, out_s16=s16,
-                             out_elems=s16.numel(), stream=cur)
-            st = status.cpu().numpy()  # (orders the decode before the next group reuses the workspace, too)
-            bad += [g[k] for k in sorted(set(b.packets["stream"][st != _lib.AA_VORBIS_OK].tolist()))]
-        return self._redo_on_host(lane, bad, pcm, total)
-
-    def _mp3_decode(self, lane, m3, comp, s16, cur):
-        """aa_mp3_decode_device over the batch's MP3 files (flat main data in
-        comp, samples into s16), in as many calls as keep one call's workspace
-        under MP3_WS_BYTES (a file alone may exceed it).  The device runs the
-        host decoder's core, damaged frames included (silence on both sides),
-        so no status is read back and no file is redone."""
-        from . import mp3_gpu as mg
-        groups, size = [[]], 0
-        for r in m3:
-            need = mg.workspace_bytes(len(r.dec.mp3.frames))
-            if groups[-1] and size + need > MP3_WS_BYTES:
-                groups.append([])
-                size = 0
-            groups[-1].append(r)
-            size += need
-        for g in groups:
-            b = mg.concat([r.dec.mp3 for r in g], [r.dec.oc for r in g], [r.dec.o16 for r in g])
-            if not len(b.frames):
-                continue
-            status = lane.flac_buffer("status", 4 * len(b.frames), torch.int32)[:4 * len(b.frames)]
-            ws = lane.flac_buffer("mp3_ws", max(mg.workspace_bytes(len(b.frames)) // 8, 1), torch.int64)
-            mg.decode_device(comp, mg.to_device(b.frames, self.dev), len(b.frames), mg.to_device(b.streams, self.dev),
-                             len(b.streams), status, ws, out_s16=s16, out_elems=s16.numel(), stream=cur)
-
     def _redo_on_host(self, lane, bad, pcm, total):
         """The files of `bad` (device-decoded, not vouched for) through
-        load_recording; returns (pcm, total) as _flac_decode describes."""
+        load_recording, the host route, whose samples -- or whose "Could not
+        load" -- then stand for them.  Returns (pcm, total): the host route may
+        decode another number of samples than the index counted (a crafted
+        stream); fewer use the head of the file's place in pcm, more move the
+        file behind the batch."""
         from . import identify_tracks as it
-        from .resample import out_length
         redone = []
         for r in bad:
             d = r.dec
@@ -554,7 +478,7 @@ class BatchAnalyser:
                 logging.error("Could not load %s", d.path, exc_info=True)
                 r.err = e if isinstance(e, ValueError) else Exception(f"Could not load {d.path}")
                 continue
-            d.flac = d.vorbis = None
+            d.codec = d.index = None
             d.f32, d.sr_in = np.ascontiguousarray(frames, dtype=np.float32), int(sr)
             n = out_length(len(d.f32), d.sr_in, SR)
             if n > d.n:  # no room in its place: behind the batch
@@ -700,39 +624,29 @@ class BatchAnalyser:
     def process(self, items, lane, pool=None):
         """items: [(file_idx, path, Decoded | Exception, sidecar meta)] -> {file_idx: document}."""
         t0 = time.time()
-        recs, failed, held = [], [], []
-        for idx, path, dec, meta in items:
-            if isinstance(dec, BaseException):
-                failed.append(_Rec(idx, str(path), None, meta, err=dec))
-            else:
-                recs.append(_Rec(idx, str(path), dec, meta))
+        recs, failed = split_items(items)
+        ok = []
         if recs:
-            held = recs
             try:
                 with torch.cuda.stream(lane.stream):
                     tm = self.timing
                     t = time.perf_counter()
                     pcm = self._upload(lane, recs)
                     t = tm.lap("upload", t)
-                    held = recs  # (their slots are returned below)
-                    failed += [r for r in recs if r.err is not None]  # a FLAC file the host route could not load
-                    recs = [r for r in recs if r.err is None]
-                    self._get_end(pcm, recs)
+                    failed += [r for r in recs if r.err is not None]  # a file the host redo could not load
+                    ok = [r for r in recs if r.err is None]
+                    self._get_end(pcm, ok)
                     t = tm.lap("get_end", t)
-                    self._signal_noise(lane, pcm, recs)
+                    self._signal_noise(lane, pcm, ok)
                     t = tm.lap("signal_noise", t)
-                    self._classify(lane, pcm, recs)
+                    self._classify(lane, pcm, ok)
                     tm.lap("classify", t)
             finally:
                 # (the slots stay held until here: band-pass filtered tracks
                 # read a recording's host samples during classify)
-                if pool is not None:
-                    for r in held:
-                        if r.dec.slot >= 0:
-                            pool.put(r.dec.slot)
-                            r.dec.slot = -1
+                return_slots(pool, recs)
         t = time.perf_counter()
-        docs = self._finish(recs + failed, t0)
+        docs = self._finish(ok + failed, t0)
         self.timing.lap("post", t)
         return docs
 
@@ -742,21 +656,25 @@ class BatchAnalyser:
         meta = None
         try:
             meta = read_sidecar(path)
-            return decode_into(path, pool, self.flac, self.vorbis, self.mp3), meta
+            return decode_into(path, pool, self.codecs), meta
         except Exception as e:
             logging.error("Could not load %s", path, exc_info=True)
             return Exception(f"Could not load {path}") if not isinstance(e, ValueError) else e, meta
 
     def run(self, jobs):
         """jobs: [(file_idx, path)] -> {file_idx: document} (the files of this rank)."""
-        import threading
-        from .analyse import read_sidecar
-        if not jobs:
-            return {}
-        if self.bird_models is None:  # examine() without models reads no audio
-            from .analyse import species_result
+        if jobs and self.bird_models is None:  # examine() without models reads no audio
+            from .analyse import read_sidecar, species_result
             return {i: dict(species_result(None, read_sidecar(p), self.analyse_tracks, False),
                             processing_time_seconds=0.0) for i, p in sorted(jobs)}
+        return self._run(jobs)
+
+    def _run(self, jobs):
+        """The run loop (CiBatchAnalyser's too): the files K at a time, decoded
+        ahead on the worker threads, each batch through process() on a lane."""
+        import threading
+        if not jobs:
+            return {}
         K = self.K
         lanes = [_Lane(self.dev) for _ in range(min(self.n_lanes, -(-len(jobs) // K)))]
         slot_bytes = max(os.path.getsize(p) for _, p in jobs) + 4096

@@ -36,7 +36,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import AA_CI_MAX_REC as MAX_REC, AA_RS_F32, AA_RS_S16
-from .batch import BatchAnalyser
+from .batch import BatchAnalyser, decode_into, return_slots, split_items
 from .cacophony_index import SAMPLE_RATE
 from .resample import out_length
 
@@ -138,19 +138,9 @@ class CiBatchAnalyser(BatchAnalyser):
 
     def __init__(self, device=None, batch=16, workers=8, lanes=2, flac=None, vorbis=None, mp3=None):
         import torch
-        from .batch import _Laps, flac_mode, mp3_mode, vorbis_mode
-        self.flac = flac_mode(flac)
-        self.vorbis = vorbis_mode(vorbis)
-        self.mp3 = mp3_mode(mp3)
-        self.bird_models = ()  # (run() only asks whether there are any to load: none here)
-        self.analyse_tracks = False
-        self.dev = torch.device(device or "cuda")
+        self._setup(device, batch, workers, lanes, flac, vorbis, mp3)
         if self.dev.index is None:  # (one spelling per device: it keys the index plan and the filter banks)
             self.dev = torch.device("cuda", torch.cuda.current_device())
-        self.K = int(batch)
-        self.workers = int(workers)
-        self.n_lanes = max(1, int(lanes))
-        self.timing = _Laps()
 
     def run(self, jobs):
         from . import cacophony_index as ci
@@ -158,14 +148,13 @@ class CiBatchAnalyser(BatchAnalyser):
             import torch
             with torch.cuda.device(self.dev):
                 ci._plan(self.dev)  # made once, before the lane threads ask for it
-        return super().run(jobs)
+        return self._run(jobs)
 
     def _load(self, path, pool):
-        from .batch import decode_into
         try:
             if str(path).endswith(".opus"):
                 return _calculate_decode(path), None  # (raises)
-            return decode_into(path, pool, self.flac, self.vorbis, self.mp3, sr_out=SAMPLE_RATE, wav_any_rate=True,
+            return decode_into(path, pool, self.codecs, sr_out=SAMPLE_RATE, wav_any_rate=True,
                                host_decode=_calculate_decode), None
         except Exception as e:
             try:  # the failure calculate() reports for this file, not the batched decoder's
@@ -187,7 +176,7 @@ class CiBatchAnalyser(BatchAnalyser):
                 logging.error("Could not load %s", d.path, exc_info=True)
                 r.err = e
                 continue
-            d.flac = d.vorbis = d.mp3 = None
+            d.codec = d.index = None
             d.f32, d.sr_in, d.n_in = np.ascontiguousarray(frames, dtype=np.float32), int(sr), len(frames)
         return pcm, total
 
@@ -195,41 +184,13 @@ class CiBatchAnalyser(BatchAnalyser):
         """The batch at 16 kHz mono in one device f32 buffer; returns (pcm, plan,
         the recordings the plan covers)."""
         import torch
-        comp_of = lambda d: d.flac is not None or d.vorbis is not None or d.mp3 is not None
-        cd = [r for r in recs if comp_of(r.dec)]
-        n16 = sum(r.dec.n_in * r.dec.channels for r in cd) + sum(r.dec.s16_t.numel() for r in recs
-                                                                  if r.dec.s16 is not None)
-        _, s16 = lane.buffers(0, n16)
-        comp = lane.flac_buffer("bytes", sum(r.dec.comp_t.numel() for r in cd), torch.uint8) if cd else None
-        cur = torch.cuda.current_stream(self.dev)
-        lane.copy.wait_stream(cur)  # the lane's previous batch is done with the buffers
-        o16 = oc = 0
-        with torch.cuda.stream(lane.copy):
-            for r in recs:
-                d = r.dec
-                if comp_of(d):
-                    comp[oc:oc + d.comp_t.numel()].copy_(d.comp_t, non_blocking=True)
-                    d.oc, d.o16 = oc, o16
-                    oc += d.comp_t.numel()
-                    o16 += d.n_in * d.channels
-                elif d.s16 is not None:
-                    s16[o16:o16 + d.s16_t.numel()].copy_(d.s16_t, non_blocking=True)
-                    d.o16 = o16
-                    o16 += d.s16_t.numel()
-        cur.wait_stream(lane.copy)
-        fl = [r for r in cd if r.dec.flac is not None]
-        vb = [r for r in cd if r.dec.vorbis is not None]
-        m3 = [r for r in cd if r.dec.mp3 is not None]
-        if fl:
-            self._flac_decode(lane, fl, comp, s16, None, 0, cur)
-        if vb:
-            self._vorbis_decode(lane, vb, comp, s16, None, 0, cur)
-        if m3:
-            self._mp3_decode(lane, m3, comp, s16, cur)
+        # (no f32 placement: pcm is laid out below, from the resample plan)
+        _, s16, comp, _, cur = self._stage(lane, recs, f32=False)
+        self._decode_compressed(lane, recs, comp, s16, cur)
         ok = [r for r in recs if r.err is None]
         # host-decoded samples (other WAV encodings, oversized files, redone files): one f32 staging buffer
         hf = [r for r in ok if r.dec.f32 is not None]
-        f32 = lane.flac_buffer("f32", sum(len(r.dec.f32) for r in hf), torch.float32) if hf else None
+        f32 = lane.scratch("f32", sum(len(r.dec.f32) for r in hf), torch.float32) if hf else None
         of = 0
         for r in hf:
             n = len(r.dec.f32)
@@ -242,7 +203,7 @@ class CiBatchAnalyser(BatchAnalyser):
                               for r in ok])
         pcm, _ = lane.buffers(max(plan.total, 1), 0)
         L = _lib.lib()
-        segs_dev = lane.flac_buffer("segments", MAX_REC * C.sizeof(_lib.RsSegment), torch.uint8)
+        segs_dev = lane.scratch("segments", MAX_REC * C.sizeof(_lib.RsSegment), torch.uint8)
         for sr, segs in plan.resample:
             resample_batch(s16, f32, [s for _, s in segs], sr, pcm, stream=cur, segs_dev=segs_dev)
         for k in plan.direct:
@@ -266,7 +227,7 @@ class CiBatchAnalyser(BatchAnalyser):
         for g in plan.groups:
             lengths = [plan.lengths[k] for k in g]
             need = int(_lib.lib().aa_ci_workspace_bytes((C.c_int64 * len(g))(*lengths), len(g)))
-            ws = lane.flac_buffer("ci_ws", max(need, 1), torch.uint8)
+            ws = lane.scratch("ci_ws", max(need, 1), torch.uint8)
             points, _ = ci.run_device(pcm, [plan.offsets[k] for k in g], lengths, workspace=ws)
             pending.append((g, lengths, points.cpu().numpy()))  # (before the next group reuses the workspace)
         for g, lengths, host in pending:
@@ -294,14 +255,8 @@ class CiBatchAnalyser(BatchAnalyser):
     def process(self, items, lane, pool=None):
         """items: [(file_idx, path, Decoded | Exception, None)] -> {file_idx: document}."""
         import torch
-        from .batch import _Rec
         t0 = time.time()
-        recs, failed = [], []
-        for idx, path, dec, meta in items:
-            if isinstance(dec, BaseException):
-                failed.append(_Rec(idx, str(path), None, meta, err=dec))
-            else:
-                recs.append(_Rec(idx, str(path), dec, meta))
+        recs, failed = split_items(items)
         ok = []
         if recs:
             try:
@@ -315,11 +270,7 @@ class CiBatchAnalyser(BatchAnalyser):
                     lane.stream.synchronize()  # every copy out of the slots has landed before they go back
                     tm.lap("index", t)
             finally:
-                if pool is not None:
-                    for r in recs:
-                        if r.dec.slot >= 0:
-                            pool.put(r.dec.slot)
-                            r.dec.slot = -1
+                return_slots(pool, recs)
         t = time.perf_counter()
         docs = self._finish(ok + failed, t0)
         self.timing.lap("post", t)

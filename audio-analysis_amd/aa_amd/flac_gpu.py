@@ -19,18 +19,13 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._codec import Slotted, read_bytes, to_device as table_to_device, u8 as _u8
 
 WG = _lib.AA_FLAC_WG  # frames one workgroup takes
 FRAME = np.dtype([("offset", "<i8"), ("out_at", "<i8"), ("nbytes", "<i4"), ("block", "<i4"), ("keep", "<i4"),
                   ("channels", "<i4"), ("bits", "<i4"), ("stream", "<i4")])
 assert FRAME.itemsize == C.sizeof(_lib.FlacFrame)
 Info = namedtuple("Info", "sample_rate channels bits_per_sample total_frames")
-
-
-def _u8(data) -> np.ndarray:
-    if isinstance(data, np.ndarray):
-        return np.ascontiguousarray(data, dtype=np.uint8)
-    return np.frombuffer(data, np.uint8)
 
 
 def index(data):
@@ -108,9 +103,39 @@ def decode_device(bytes_dev, table_dev, n_frames, status_dev, ws, out_i32=None, 
         _lib.stream_ptr(stream)), "aa_flac_decode_device")
 
 
-def table_to_device(table, device):
-    t = torch.from_numpy(np.ascontiguousarray(table).view(np.uint8).reshape(-1).copy())
-    return t.to(device)
+def sniff(buf, size) -> bool:
+    from .audio import _is_flac
+    return _is_flac(buf, size)
+
+
+def index_slot(buf, size):
+    """Slotted of the FLAC file in buf[:size] (it stays there as it is), or None:
+    not indexable, no frames, or frames too large for a batch (fits_batch)."""
+    ix = index(buf[:size])
+    if ix is None or ix[0].total_frames <= 0 or not fits_batch(ix[1]):
+        return None
+    info, tab = ix
+    return Slotted(tab, int(size), info.total_frames, info.channels, info.sample_rate)
+
+
+def decode_batch(scratch, items, byte_bases, out_bases, comp, s16, device, stream):
+    """One aa_flac_decode_device over the frame tables ``items`` (file k's bytes
+    at comp[byte_bases[k]:], its samples into s16[out_bases[k]:]), then the
+    per-frame statuses, read back before any sample is used: the positions of
+    the files with a frame not OK.  scratch(name, n, dtype): device buffers."""
+    tab = concat(items, byte_bases, out_bases)
+    status = scratch("status", len(tab), torch.int32)[:len(tab)]
+    ws = scratch("ws", max(workspace_bytes(tab) // 4, 1), torch.int32)
+    decode_device(comp, table_to_device(tab, device), len(tab), status, ws, out_s16=s16, stream=stream)
+    st = status.cpu().numpy()
+    return sorted(set(tab["stream"][st != _lib.AA_FLAC_OK].tolist()))
+
+
+def host_samples(decoded):
+    """The host decode of a Decoded's slot (the file's bytes), mono float32."""
+    from .audio import _to_mono, decode_flac
+    q, ch, _ = decode_flac(decoded.comp_t.numpy().tobytes())
+    return _to_mono(q, ch)
 
 
 def _host_route(data, device):
@@ -125,11 +150,7 @@ def decode_to_device(data_or_path, device=None):
     on the device.  Any frame the device does not vouch for sends the whole
     file through ``audio.decode_flac`` (its samples, or its exception)."""
     device = torch.device(device or "cuda")
-    if isinstance(data_or_path, (bytes, bytearray, memoryview, np.ndarray)):
-        data = data_or_path
-    else:
-        with open(data_or_path, "rb") as f:
-            data = f.read()
+    data = read_bytes(data_or_path)
     ix = index(data)
     if ix is None:
         return _host_route(data, device)

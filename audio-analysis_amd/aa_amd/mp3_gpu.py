@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._codec import groups_under, read_bytes, reread_samples as host_samples, slot_stream, to_device, u8 as _u8
 
 WG = _lib.AA_MP3_WG
 # side info fields: [granule * 2 + channel] (table_select / subblock_gain: three values each)
@@ -44,12 +45,6 @@ Indexed = namedtuple("Indexed", "stream frames payload")
 Batch = namedtuple("Batch", "frames streams")
 
 _TABLES = {}  # device -> the table blob there
-
-
-def _u8(data) -> np.ndarray:
-    if isinstance(data, np.ndarray):
-        return np.ascontiguousarray(data, dtype=np.uint8)
-    return np.frombuffer(data, np.uint8)
 
 
 def index_rc(data, payload=None):
@@ -156,12 +151,6 @@ def decode_frames_host(payload, frames, streams, want_f32=True, want_s16=True, n
     return f32, s16, status
 
 
-def to_device(table, device):
-    """A host table (FRAME / STREAM records) as device bytes."""
-    t = torch.from_numpy(np.ascontiguousarray(table).view(np.uint8).reshape(-1).copy())
-    return t.to(device)
-
-
 def decode_device(bytes_dev, frames_dev, n_frames, streams_dev, n_streams, status_dev, ws, out_s16=None,
                   out_f32=None, out_elems=None, stream=None):
     """One aa_mp3_decode_device call over device tensors (no synchronisation).
@@ -175,17 +164,44 @@ def decode_device(bytes_dev, frames_dev, n_frames, streams_dev, n_streams, statu
         _lib.stream_ptr(stream)), "aa_mp3_decode_device")
 
 
+WS_BYTES = 1 << 30  # workspace one aa_mp3_decode_device call of a batch may take (sixteen 60 s clips: about 0.86 GB)
+
+
+def sniff(buf, size) -> bool:
+    from .audio import _is_mp3
+    return _is_mp3(buf, size)
+
+
+def index_slot(buf, size):
+    """Slotted of the MP3 file in buf[:size], whose flat main data the index
+    writes over the head of buf, or None (_codec.slot_stream)."""
+    return slot_stream(index(buf[:size], payload=buf), fits_batch)
+
+
+def decode_batch(scratch, items, byte_bases, out_bases, comp, s16, device, stream):
+    """aa_mp3_decode_device over the Indexed ``items`` (file k's main data at
+    comp[byte_bases[k]:], its samples into s16[out_bases[k]:]), in as many calls
+    as keep one call's workspace under WS_BYTES (a file alone may exceed it).
+    The device runs the host decoder's core, damaged frames included (silence
+    on both sides), so no status is read back and no file is in doubt: []."""
+    for g in groups_under([workspace_bytes(len(ix.frames)) for ix in items], WS_BYTES):
+        b = concat([items[k] for k in g], [byte_bases[k] for k in g], [out_bases[k] for k in g])
+        if not len(b.frames):
+            continue
+        status = scratch("status", 4 * len(b.frames), torch.int32)[:4 * len(b.frames)]
+        ws = scratch("mp3_ws", max(workspace_bytes(len(b.frames)) // 8, 1), torch.int64)
+        decode_device(comp, to_device(b.frames, device), len(b.frames), to_device(b.streams, device),
+                      len(b.streams), status, ws, out_s16=s16, out_elems=s16.numel(), stream=stream)
+    return []
+
+
 def decode_to_device(data_or_path, device=None):
     """An MP3 file (path or bytes) -> (mono float32 PCM on the device at the
     file's own rate, sample rate): the samples ``audio.decode`` gives, decoded
     on the device.  A stream the index declines raises as ``audio.decode_mp3``
     does."""
     device = torch.device(device or "cuda")
-    if isinstance(data_or_path, (bytes, bytearray, memoryview, np.ndarray)):
-        data = data_or_path
-    else:
-        with open(data_or_path, "rb") as f:
-            data = f.read()
+    data = read_bytes(data_or_path)
     rc, ix = index_rc(data)
     if ix is None:
         _lib.check(rc, "aa_mp3_index")

@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._codec import groups_under, read_bytes, reread_samples as host_samples, slot_stream, to_device, u8 as _u8
 
 WG = _lib.AA_VORBIS_WG  # packets one unpack workgroup takes
 PACKET = np.dtype([("offset", "<i8"), ("pos", "<i8"), ("blk_at", "<i8"), ("nbytes", "<i4"), ("n", "<i4"),
@@ -41,12 +42,6 @@ Indexed = namedtuple("Indexed", "stream packets payload setup")
 Batch = namedtuple("Batch", "packets streams setups n_setups")
 
 _GUESS = {"setup": 1 << 20}  # bytes a flattened setup has needed so far (grow-only)
-
-
-def _u8(data) -> np.ndarray:
-    if isinstance(data, np.ndarray):
-        return np.ascontiguousarray(data, dtype=np.uint8)
-    return np.frombuffer(data, np.uint8)
 
 
 def index_rc(data, payload=None):
@@ -167,12 +162,6 @@ def decode_packets_host(payload, packets, streams, setups, want_f32=True, want_s
     return f32, s16, status
 
 
-def to_device(table, device):
-    """A host table (PACKET / STREAM records, or setup bytes) as device bytes."""
-    t = torch.from_numpy(np.ascontiguousarray(table).view(np.uint8).reshape(-1).copy())
-    return t.to(device)
-
-
 def decode_device(bytes_dev, packets_dev, n_packets, streams_dev, n_streams, setups_dev, pl, status_dev, ws,
                   out_s16=None, out_f32=None, out_elems=None, stream=None):
     """One aa_vorbis_decode_device call over device tensors (no synchronisation).
@@ -184,6 +173,41 @@ def decode_device(bytes_dev, packets_dev, n_packets, streams_dev, n_streams, set
         int(n_streams), _lib.dptr(setups_dev), setups_dev.numel() * setups_dev.element_size(), C.byref(pl),
         _lib.dptr(out_s16), _lib.dptr(out_f32), int(out_elems), _lib.dptr(status_dev), _lib.dptr(ws),
         ws.numel() * ws.element_size(), _lib.stream_ptr(stream)), "aa_vorbis_decode_device")
+
+
+WS_BYTES = 1 << 30  # workspace one aa_vorbis_decode_device call of a batch may take
+
+
+def sniff(buf, size) -> bool:
+    return size >= 4 and bytes(buf[:4]) == b"OggS"
+
+
+def index_slot(buf, size):
+    """Slotted of the Ogg Vorbis file in buf[:size], whose packet bytes the
+    index writes over the head of buf, or None (_codec.slot_stream)."""
+    return slot_stream(index(buf[:size], payload=buf), fits_batch)
+
+
+def decode_batch(scratch, items, byte_bases, out_bases, comp, s16, device, stream):
+    """aa_vorbis_decode_device over the Indexed ``items`` (file k's packet bytes
+    at comp[byte_bases[k]:], its samples into s16[out_bases[k]:]), in as many
+    calls as keep one call's workspace under WS_BYTES (a file alone may exceed
+    it); after each the per-packet statuses, read back before any sample is
+    used: the positions of the files with a packet not OK."""
+    bad = []
+    for g in groups_under([workspace_bytes(ix.packets, ix.stream) for ix in items], WS_BYTES):
+        b = concat([items[k] for k in g], [byte_bases[k] for k in g], [out_bases[k] for k in g])
+        if not len(b.packets):
+            continue
+        pl, nb = plan(b.packets, b.streams)
+        status = scratch("status", len(b.packets), torch.int32)[:len(b.packets)]
+        ws = scratch("vorbis_ws", max(nb // 8, 1), torch.int64)
+        decode_device(comp, to_device(b.packets, device), len(b.packets), to_device(b.streams, device),
+                      len(b.streams), to_device(b.setups, device), pl, status, ws, out_s16=s16,
+                      out_elems=s16.numel(), stream=stream)
+        st = status.cpu().numpy()  # (orders the decode before the next group reuses the workspace, too)
+        bad += [g[k] for k in sorted(set(b.packets["stream"][st != _lib.AA_VORBIS_OK].tolist()))]
+    return bad
 
 
 def _host_route(data, device):
@@ -199,11 +223,7 @@ def decode_to_device(data_or_path, device=None):
     device does not vouch for, sends the whole file through
     ``audio.decode_vorbis`` (its samples, or its exception)."""
     device = torch.device(device or "cuda")
-    if isinstance(data_or_path, (bytes, bytearray, memoryview, np.ndarray)):
-        data = data_or_path
-    else:
-        with open(data_or_path, "rb") as f:
-            data = f.read()
+    data = read_bytes(data_or_path)
     ix = index(data)
     if ix is None:
         return _host_route(data, device)

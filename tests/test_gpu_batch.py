@@ -106,6 +106,56 @@ def test_batch_matches_per_file_analyse_tracks(gpu, model_root, tmp_path):
     assert per_file[0]["species_identify"] and not per_file[4]["species_identify"]
 
 
+def test_mixed_format_batch_gpu_modes_match_host_modes(gpu, model_root, tmp_path, monkeypatch):
+    """Every device codec in one batch: a WAV, two FLAC files (one stereo, 24-bit,
+    44.1 kHz), two Ogg Vorbis files (one stereo 44.1 kHz) and a 44.1 kHz MP3
+    file, four per batch on one lane -- a full batch in which the three formats
+    share the compressed buffer (Vorbis and MP3 at non-zero bases) and a partial
+    one; files off 48 kHz take the resample branch."""
+    import flac_writer as fw
+    import mp3_cases as mc
+    import mp3_writer as mw
+    import vorbis_cases as vc
+    import vorbis_writer as vw
+    from aa_amd import corpus, flac_gpu, mp3_gpu, vorbis_gpu
+    from aa_amd.batch import BatchAnalyser
+    from tools import synth
+
+    def flac(name, seed, sr, bits, stereo):
+        y = np.round(synth.clip(seed, seconds=3.0, sr=sr) * (1 << (bits - 1))).astype(np.int64)
+        y = np.clip(y, -(1 << (bits - 1)), (1 << (bits - 1)) - 1)
+        chans = [y, y[::-1] // 2] if stereo else [y]
+        frames = [fw.frame([c[i:i + 4096] for c in chans], bits, sr, k, "mid_side" if stereo else "indep")
+                  for k, i in enumerate(range(0, len(y), 4096))]
+        (tmp_path / name).write_bytes(fw.stream(frames, sr, len(chans), bits, len(y), 4096))
+
+    flac("f1.flac", 601, 48000, 16, False)
+    x = synth.clip(602, seconds=0.6, sr=44100)
+    (tmp_path / "v2.ogg").write_bytes(vc.repeat(vw.encode(np.stack([x, 0.5 * x[::-1]], 1), sr=44100,
+                                                          schedule=[1, 1, 1, 0], residue_type=2), 5))
+    synth.write_wav(tmp_path / "w.wav", synth.clip(603, seconds=3.0))
+    c = mc.case("mono_long")  # 44.1 kHz; 120 frames: 3.1 s
+    (tmp_path / "m.mp3").write_bytes(mw.stream(list(c["frames"]) * 30, sr_index=c["sr_index"], channels=c["channels"]))
+    flac("f2.flac", 604, 44100, 24, True)
+    (tmp_path / "v1.ogg").write_bytes(vc.repeat(vw.encode(synth.clip(605, seconds=0.6), sr=48000,
+                                                          schedule=[1, 1, 0, 0, 1]), 5))
+    files = [str(tmp_path / n) for n in ("f1.flac", "v2.ogg", "w.wav", "m.mp3", "f2.flac", "v1.ogg")]
+    calls = {}
+    for name, mod in (("flac", flac_gpu), ("vorbis", vorbis_gpu), ("mp3", mp3_gpu)):
+        def counted(*a, _real=mod.decode_device, _name=name, **kw):
+            calls[_name] = calls.get(_name, 0) + 1
+            return _real(*a, **kw)
+        monkeypatch.setattr(mod, "decode_device", counted)
+    models = [str(model_root / "model1" / "audioModel.keras")]
+    jobs = list(enumerate(files))
+    host = BatchAnalyser(models, False, device=gpu, batch=4, lanes=1, flac="host", vorbis="host", mp3="host").run(jobs)
+    assert not calls
+    dev = BatchAnalyser(models, False, device=gpu, batch=4, lanes=1, flac="gpu", vorbis="gpu", mp3="gpu").run(jobs)
+    assert calls["flac"] >= 1 and calls["vorbis"] >= 1 and calls["mp3"] >= 1
+    assert _docs(dev) == _docs(host)
+    assert sorted(dev) == list(range(6)) and all(corpus.FAILED not in d for d in dev.values())
+
+
 def test_pcm_s16_to_f32_matches_host_decode(gpu):
     """aa_pcm_s16_to_f32 == audio._to_mono (ffmpeg s16 / 32768, channel mean) bit for bit."""
     import torch
