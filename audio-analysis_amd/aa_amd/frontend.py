@@ -5,6 +5,7 @@ group configures it, src/identify_tracks.py:465-497).  ``run`` takes the whole
 recording resident on the device plus a device table of window views and
 returns ``[n_win, n_mels, T, channels]`` float32 -- the stack of what
 ``get_spect`` returns per window (src/identify_tracks.py:212-288).
+``n_fft`` is a power of two from 256 to 8192 (aa_fe_create refuses the rest).
 """
 from __future__ import annotations
 

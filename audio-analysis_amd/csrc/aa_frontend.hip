@@ -397,6 +397,306 @@ __global__ __launch_bounds__(NFFT / 16) void fe_stft_mel(
 }
 
 // ---------------------------------------------------------------------------
+// fe_stft_mel_small: n_fft 256, 512 and 1024 -- the same contract as
+// fe_stft_mel (window views, normalize_sample, centre padding, periodic Hann,
+// f32, pow_mag, CSR mel rows, melS[w][t][m]), shaped for short transforms at
+// short hops: a frame belongs to a GROUP of G = NC/8 lanes (64, 32 or 16), so
+// a wave carries 64/G = 1, 2 or 4 frames and a frame never spans waves.  The
+// transform is three Stockham passes, radix 8 (NS = 1, from the samples),
+// radix 8 (NS = 8) and radix NC/64 = 8, 4 or 2 (NS = 64), ping-ponging
+// between the group's two LDS buffers with wave_sync() between passes; the
+// block-wide barriers are the two around the staging of the PCM span.
+//
+// Block = 4 waves on fe_small_fpb() consecutive frames of one window (8 at
+// 1024, 16 below: 2, 2 or 1 rounds of 4, 8 or 16 frames).  Their overlapped
+// PCM span is loaded and normalised once into LDS when (fpb - 1) hop + n_fft
+// fits kSmallSeg samples; otherwise (hop well above n_fft) every lane loads
+// and normalises its own 16 samples from global memory.  Each wave writes one
+// partial maximum per item: blkmax[w][fb][wave].  The span budget and the
+// register bound (3 waves per SIMD) are set so that three blocks share a CU
+// at the usual filterbanks (48 KiB + CSR <= 53 KiB of LDS each).
+//
+// LDS banks (ds_read_b32 / stores: word mod 32 per half-wave or 16-lane
+// store group; ds_read_b64: word mod 64 per half-wave):
+//   span      even samples in segE, odd samples in segO = segE + kSmallHalf,
+//             kSmallHalf = 16 mod 32: the staging stores (lane q -> word q/2
+//             of either half) and the pass-1 reads (lane n -> word n of each
+//             half, whatever the parity of the frame's start) are
+//             conflict-free; the interleaved layout of fe_stft_mel reads at
+//             stride 2, 2-way.
+//   passes    pidx() pads one float2 per 8.  The scatters of pass 1 (float2
+//             stride 9) and pass 2 (rows of 8 at stride 72) are conflict-free;
+//             pass 3 stores runs of consecutive points, where the pad makes 1
+//             or 2 of 16 lanes wrap onto a used bank: 2-way, inside the store's
+//             own issue time.  The gathers of passes 2 and 3 and the real
+//             split read 32 consecutive points per half-wave across 4 pads
+//             (36 float2 slots over 32): 3 or 4 lanes share a bank 2-way, so
+//             such a ds_read_b64 takes 2 LDS cycles per half-wave instead of
+//             1.  At n_fft 256 the two groups of a half-wave sit 144 float2
+//             apart (16 mod 32) and overlap by 2 slots the same way.
+//   mel rows  a lane per band: the rows' offsets and lengths set the banks
+//             (neighbouring triangles overlap by half), as in fe_stft_mel.
+// ---------------------------------------------------------------------------
+constexpr int kSmallWaves = 4;                    // waves per block
+constexpr int kSmallSeg = 3072;                   // shared PCM span, samples
+constexpr int kSmallHalf = kSmallSeg / 2 + 16;    // words per parity half (16 mod 32)
+constexpr int kSmallBuf = 64 * 9;                 // float2 per wave buffer: 512 points + pidx padding
+__host__ __device__ constexpr int fe_small_fpb(int n_fft) { return n_fft == 1024 ? 8 : 16; }
+__host__ __device__ constexpr bool fe_small_shared(int n_fft, int hop) {
+    return (long long)(fe_small_fpb(n_fft) - 1) * hop + n_fft <= kSmallSeg;
+}
+
+// Pass<> for a group of G lanes inside a wave: butterflies j = gl + b*G.
+template <int NC, int R, int G, int NS>
+struct GroupPass {
+    static constexpr int NB = NC / R;
+    static constexpr int PER = NB / G;
+    static_assert(NB % G == 0 && NB % 8 == 0 && NS % 8 == 0, "whole butterflies per lane, strides of whole pads");
+    float2 t[PER][R - 1];
+    __device__ __forceinline__ void load(const float2* __restrict__ tw, int gl) {
+#pragma unroll
+        for (int b = 0; b < PER; ++b) {
+            const int k = (gl + b * G) % NS;
+#pragma unroll
+            for (int r = 1; r < R; ++r) t[b][r - 1] = tw[(r * k * (NC / (NS * R))) & (NC - 1)];
+        }
+    }
+    __device__ __forceinline__ void run(const float2* __restrict__ src, float2* __restrict__ dst, int gl) const {
+#pragma unroll
+        for (int b = 0; b < PER; ++b) {
+            const int j = gl + b * G;
+            // NB and NS are multiples of 8, so pidx(i + 8c) = pidx(i) + 9c: one
+            // address per butterfly side, the rest immediate offsets
+            const float2* s0 = src + pidx(j);
+            float2 v[R];
+#pragma unroll
+            for (int r = 0; r < R; ++r) v[r] = s0[r * (NB + NB / 8)];
+#pragma unroll
+            for (int r = 1; r < R; ++r) v[r] = cmul(v[r], t[b][r - 1]);
+            if constexpr (R == 8) dft8(v);
+            if constexpr (R == 4) dft4(v[0], v[1], v[2], v[3]);
+            if constexpr (R == 2) dft2(v[0], v[1]);
+            const int k = j % NS;
+            float2* d0 = dst + pidx((j / NS) * NS * R + k);
+#pragma unroll
+            for (int r = 0; r < R; ++r) d0[r * (NS + NS / 8)] = v[r];
+        }
+    }
+};
+
+template <int NFFT, int PM>
+__global__ __launch_bounds__(64 * kSmallWaves, 3) void fe_stft_mel_small(
+    const float* __restrict__ pcm, const aa_window* __restrict__ wins, const float4* __restrict__ stats,
+    const float* __restrict__ hann, const float2* __restrict__ tw, const float2* __restrict__ tw2,
+    const int4* __restrict__ rows, const float* __restrict__ vals, int nnz, int win_len, int hop, int T,
+    int n_mels, int kmin, int kmax, int normalize, float power, int nblk, int n_items,
+    float* __restrict__ melS, float* __restrict__ blkmax) {
+    constexpr int NC = NFFT / 2;
+    constexpr int G = NC / 8;             // lanes per frame
+    constexpr int FPW = 64 / G;           // frames per wave
+    constexpr int FPR = kSmallWaves * FPW;  // frames per round of the block
+    constexpr int FPB = fe_small_fpb(NFFT);
+    constexpr int NCP = NC + NC / 8;      // padded group buffer (float2); FPW * NCP == kSmallBuf
+    constexpr int KB = 9;                 // bins per lane: NC + 1 over G lanes
+    static_assert(NC == 128 || NC == 256 || NC == 512, "NFFT 256..1024");
+    static_assert(FPB % FPR == 0 && FPW * NCP == kSmallBuf, "rounds of whole waves");
+    extern __shared__ float lds[];
+    float* segE = lds;                    // even samples of the span
+    float* segO = lds + kSmallHalf;       // odd samples
+    float2* bufs = reinterpret_cast<float2*>(lds + 2 * kSmallHalf);
+    int4* srows = reinterpret_cast<int4*>(bufs + kSmallWaves * 2 * kSmallBuf);
+    float* svals = reinterpret_cast<float*>(srows + n_mels);
+
+    const int tid = threadIdx.x;
+    const int wv = tid >> 6, lane = tid & 63;
+    const int g = lane / G, gl = lane % G;
+    float2* bufA = bufs + wv * 2 * kSmallBuf + g * NCP;
+    float2* bufB = bufA + kSmallBuf;
+
+    // --- per-thread constants, loaded once per block ---
+    float hw[8][2];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+        const float2 h = reinterpret_cast<const float2*>(hann)[gl + r * G];
+        hw[r][0] = h.x;
+        hw[r][1] = h.y;
+    }
+    GroupPass<NC, 8, G, 8> p2;
+    GroupPass<NC, NC / 64, G, 64> p3;
+    p2.load(tw, gl);
+    p3.load(tw, gl);
+    float2 w2r[KB];
+#pragma unroll
+    for (int i = 0; i < KB; ++i) w2r[i] = tw2[min(kmin + gl + i * G, kmax)];
+    for (int i = tid; i < n_mels; i += 64 * kSmallWaves) srows[i] = rows[i];
+    for (int i = tid; i < nnz; i += 64 * kSmallWaves) svals[i] = vals[i];
+    const bool shared = fe_small_shared(NFFT, hop);  // the span fits: stage it once
+    __syncthreads();
+
+    // persistent loop over (window, frame block) items
+    for (int item = blockIdx.x; item < n_items; item += gridDim.x) {
+        const int w = item / nblk;
+        const int fb = item - w * nblk;
+        const int f0 = fb * FPB;
+        const int nf = min(FPB, T - f0);
+        // --- normalisation constants (normalize_data, :203-208) ---
+        const aa_window d = wins[w];
+        float lo = INFINITY, hi = -INFINITY;
+#pragma unroll
+        for (int s = 0; s < kStatSplit; ++s) {
+            const float4 st = stats[w * kStatSplit + s];
+            lo = fminf(lo, st.x);
+            hi = fmaxf(hi, st.y);
+        }
+        const float scale = __fsub_rn(hi, lo);  // == max(x - min) (monotone rounding)
+        const float inv = __fdiv_rn(1.f, scale);
+        const long long safe = d.n_valid > 0 ? d.src : 0;  // any in-bounds sample
+        // sample i of the centre-padded window: np.pad zeros outside the view,
+        // normalised inside the window, 0 on the centre padding
+        auto in_view = [&](int i) {
+            const int rel = i - d.pad_left;
+            return i >= 0 && i < win_len && rel >= 0 && rel < d.n_valid;
+        };
+        auto finish = [&](int i, bool ok, float raw) {
+            float v = 0.f;
+            if (i >= 0 && i < win_len) {
+                v = ok ? raw : 0.f;
+                if (normalize) v = normalize_sample(v, lo, scale, inv);
+            }
+            return v;
+        };
+
+        if (shared) {
+            __syncthreads();  // the previous item's frames have read their span
+            const int seg_len = (nf - 1) * hop + NFFT;
+            const int base = f0 * hop - NFFT / 2;  // window index of the span's first sample
+            constexpr int SEGU = 4;
+            for (int q0 = 0; q0 < seg_len; q0 += SEGU * 64 * kSmallWaves) {
+                float raw[SEGU];
+                bool ok[SEGU];
+#pragma unroll
+                for (int u = 0; u < SEGU; ++u) {  // unconditional loads from clamped addresses
+                    const int q = q0 + u * 64 * kSmallWaves + tid;
+                    ok[u] = q < seg_len && in_view(base + q);
+                    raw[u] = pcm[ok[u] ? d.src + (base + q - d.pad_left) : safe];
+                }
+#pragma unroll
+                for (int u = 0; u < SEGU; ++u) {
+                    const int q = q0 + u * 64 * kSmallWaves + tid;
+                    if (q < seg_len) ((q & 1) ? segO : segE)[q >> 1] = finish(base + q, ok[u], raw[u]);
+                }
+            }
+            __syncthreads();
+        }
+
+        float bmax = 0.f;
+#pragma unroll 1
+        for (int rd = 0; rd < FPB / FPR; ++rd) {
+            const int fw = rd * FPR + wv * FPW;  // the wave's first frame of this round
+            if (fw >= nf) break;                 // wave-uniform: no frame left for this wave
+            // a group past the last frame repeats it (uniform control flow) and stores nothing
+            const bool live = fw + g < nf;
+            const int fr = min(fw + g, nf - 1);
+            // pass 1 (NS = 1) straight from the samples: z[n] = xw[2n] + i xw[2n+1]
+            {
+                float2 v[8];
+                if (shared) {
+                    const int s = fr * hop;  // span index of the frame's first sample
+                    const float* pe = (s & 1) ? segO + (s >> 1) : segE + (s >> 1);      // x[2n]
+                    const float* po = (s & 1) ? segE + ((s + 1) >> 1) : segO + (s >> 1);  // x[2n+1]
+#pragma unroll
+                    for (int r = 0; r < 8; ++r) {
+                        const int n = gl + r * G;
+                        v[r] = make_float2(pe[n] * hw[r][0], po[n] * hw[r][1]);
+                    }
+                } else {
+                    const int i0 = (f0 + fr) * hop - NFFT / 2 + 2 * gl;
+                    float raw[8][2];
+                    bool ok[8][2];
+#pragma unroll
+                    for (int r = 0; r < 8; ++r) {
+#pragma unroll
+                        for (int e = 0; e < 2; ++e) {
+                            const int i = i0 + 2 * r * G + e;
+                            ok[r][e] = in_view(i);
+                            raw[r][e] = pcm[ok[r][e] ? d.src + (i - d.pad_left) : safe];
+                        }
+                    }
+#pragma unroll
+                    for (int r = 0; r < 8; ++r) {
+                        const int i = i0 + 2 * r * G;
+                        v[r] = make_float2(finish(i, ok[r][0], raw[r][0]) * hw[r][0],
+                                           finish(i + 1, ok[r][1], raw[r][1]) * hw[r][1]);
+                    }
+                }
+                dft8(v);
+#pragma unroll
+                for (int r = 0; r < 8; ++r) bufA[pidx(gl * 8 + r)] = v[r];
+            }
+            wave_sync();
+            p2.run(bufA, bufB, gl);
+            wave_sync();
+            p3.run(bufB, bufA, gl);
+            wave_sync();
+            const float2* Z = bufA;                        // natural order
+            const float2* zk = Z + pidx(kmin + gl);        // Z[k] of the lane's first bin
+            const float2* zm = Z + pidx(NC - kmin - gl);   // its mirror (read only while k <= kmax <= NC)
+            float* Pf = reinterpret_cast<float*>(bufB);    // free buffer: |X|^p of bins kmin..kmax
+#pragma unroll
+            for (int i = 0; i < KB; ++i) {
+                const int k = kmin + gl + i * G;
+                if (k <= kmax) {
+                    float re, im;
+                    if (k == 0 || k == NC) {
+                        const float2 z0 = Z[0];  // pidx(0) == 0
+                        re = (k == 0) ? z0.x + z0.y : z0.x - z0.y;
+                        im = 0.f;
+                    } else {
+                        // (G is a multiple of 8: pidx(k) = pidx(kmin + gl) + 9 i G / 8)
+                        const float2 a = zk[i * (G + G / 8)];
+                        const float2 b = zm[-i * (G + G / 8)];  // Z[NC - k]; conj taken below
+                        // E = (a + conj b)/2 ; O = -i (a - conj b)/2 ; X = E + W^k O
+                        const float2 E = make_float2(0.5f * (a.x + b.x), 0.5f * (a.y - b.y));
+                        const float2 O = make_float2(0.5f * (a.y + b.y), -0.5f * (a.x - b.x));
+                        const float2 X = cadd(E, cmul(w2r[i], O));
+                        re = X.x;
+                        im = X.y;
+                    }
+                    Pf[k - kmin] = pow_mag<PM>(re, im, power);
+                }
+            }
+            wave_sync();
+            // mel rows: a lane per band, one contiguous row of melS per frame
+            float* orow = melS + ((size_t)w * T + f0 + fr) * n_mels;
+            for (int m = gl; m < n_mels; m += G) {
+                const int4 rw = srows[m];
+                const float* wvp = svals + rw.z;
+                const float* pv = Pf + (rw.x - kmin);
+                float s = 0.f;
+                // predicated 8-wide chunks: all LDS reads of a chunk in flight at once
+                for (int i0 = 0; i0 < rw.y; i0 += 8) {
+                    float a[8], b[8];
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) {
+                        const int ii = min(i0 + i, rw.y - 1);  // unconditional LDS reads
+                        a[i] = (i0 + i < rw.y) ? wvp[ii] : 0.f;
+                        b[i] = pv[ii];
+                    }
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) s = fmaf(a[i], b[i], s);
+                }
+                if (live) orow[m] = s;
+                bmax = fmaxf(bmax, s);  // (a repeated frame repeats its values)
+            }
+            // the next round writes bufA first (read last before the wave_sync
+            // above) and bufB only after its own first wave_sync
+        }
+        bmax = wave_max(bmax);
+        if (lane == 0) blkmax[(size_t)w * nblk * kSmallWaves + fb * kSmallWaves + wv] = bmax;
+    }  // item loop
+}
+
+// ---------------------------------------------------------------------------
 // fe_stft_mel_4096: the n_fft = 4096 path, one WAVE per frame, waves
 // independent of each other (no block-level synchronisation after the
 // prologue).
@@ -980,6 +1280,33 @@ static int launch_stft(const FePlan& p, const float* pcm, const aa_window* wins,
     return AA_OK;
 }
 
+// n_fft 256, 512 and 1024 run fe_stft_mel_small
+static bool fe_small(const FePlan& p) { return p.cfg.n_fft <= 1024; }
+
+// its LDS does not depend on the hop: span halves | wave buffers | CSR rows | values
+static size_t fe_lds_bytes_small(const FePlan& p) {
+    return sizeof(float) * 2 * (size_t)kSmallHalf + sizeof(float2) * (size_t)kSmallWaves * 2 * kSmallBuf +
+           sizeof(int4) * (size_t)p.cfg.n_mels + sizeof(float) * (size_t)std::max(p.nnz, 1);
+}
+
+template <int NFFT, int PM>
+static int launch_stft_small(const FePlan& p, const float* pcm, const aa_window* wins, int n_win,
+                             const float4* stats, float* melS, float* blkmax, hipStream_t st) {
+    const size_t lds = fe_lds_bytes_small(p);
+    AA_DYN_LDS((fe_stft_mel_small<NFFT, PM>), lds);
+    const int nblk = p.nfblk / kSmallWaves;  // frame blocks per window
+    const int n_items = nblk * n_win;
+    // persistent grid: as many blocks as are resident together on 256 CUs
+    // (LDS allows 3 at most, the kernel's register bound keeps 3 waves per SIMD)
+    const int per_cu = std::max(1, (int)((160 * 1024) / (lds + 256)));
+    const int grid = std::min(n_items, 256 * per_cu);
+    hipLaunchKernelGGL((fe_stft_mel_small<NFFT, PM>), dim3(grid), dim3(64 * kSmallWaves), lds, st, pcm, wins,
+                       stats, p.d_win, p.d_tw, p.d_tw2, p.d_rows, p.d_vals, p.nnz, p.cfg.win_len, p.cfg.hop, p.T,
+                       p.cfg.n_mels, p.kmin, p.kmax, p.cfg.normalize, p.cfg.power, nblk, n_items, melS, blkmax);
+    AA_LAUNCH_CHECK();
+    return AA_OK;
+}
+
 // the wave-per-frame kernel covers n_fft 4096 whenever the kept band fits the
 // per-wave buffer (15 bins per lane)
 static bool fe_fast4096(const FePlan& p) {
@@ -1044,8 +1371,8 @@ using namespace aa;
 extern "C" int aa_fe_create(const aa_fe_config* cfg, const float* melfb, void** plan) {
     AA_CHECK(cfg && melfb && plan, AA_ERR_INVALID, "aa_fe_create: null argument");
     const int n = cfg->n_fft;
-    AA_CHECK(n == 2048 || n == 4096 || n == 8192, AA_ERR_UNSUPPORTED,
-             "aa_fe_create: n_fft %d not supported (power of two 2048..8192)", n);
+    AA_CHECK(n >= 256 && n <= 8192 && (n & (n - 1)) == 0, AA_ERR_UNSUPPORTED,
+             "aa_fe_create: n_fft %d not supported (power of two 256..8192)", n);
     AA_CHECK(cfg->hop > 0 && cfg->win_len > 0 && cfg->n_mels > 0 && cfg->channels >= 1 &&
                  (cfg->out_f16 == 0 || cfg->out_f16 == 1),
              AA_ERR_INVALID, "aa_fe_create: bad sizes");
@@ -1075,7 +1402,9 @@ extern "C" int aa_fe_create(const aa_fe_config* cfg, const float* melfb, void** 
     p->kmax = kmax;
     p->nnz = (int)vals.size();
     // per-window partial maxima: one per frame block of whichever kernel runs
-    p->nfblk = fe_fast4096(*p) ? p->T : (p->T + kFpb - 1) / kFpb;
+    p->nfblk = fe_small(*p)      ? (p->T + fe_small_fpb(n) - 1) / fe_small_fpb(n) * kSmallWaves
+               : fe_fast4096(*p) ? p->T
+                                 : (p->T + kFpb - 1) / kFpb;
     if (vals.empty()) vals.push_back(0.f);
     const int nc = n / 2;
     std::vector<float> win(n);
@@ -1142,8 +1471,14 @@ extern "C" int aa_fe_create(const aa_fe_config* cfg, const float* melfb, void** 
         aa_fe_destroy(p);
         return AA_ERR_HIP;
     }
-    AA_CHECK(fe_lds_bytes(*p) <= 150 * 1024, AA_ERR_UNSUPPORTED,
-             "aa_fe_create: hop %d too large for the LDS segment", cfg->hop);
+    // (fe_stft_mel_small takes any hop: past its shared span, frames load their own samples)
+    const bool fits = fe_small(*p) ? fe_lds_bytes_small(*p) <= 160 * 1024 : fe_lds_bytes(*p) <= 150 * 1024;
+    if (!fits) {
+        if (fe_small(*p)) set_error("aa_fe_create: filterbank (%d bands, %d weights) too large for the LDS", cfg->n_mels, p->nnz);
+        else set_error("aa_fe_create: hop %d too large for the LDS segment", cfg->hop);
+        aa_fe_destroy(p);
+        return AA_ERR_UNSUPPORTED;
+    }
     *plan = p;
     return AA_OK;
 }
@@ -1209,6 +1544,9 @@ extern "C" int aa_fe_run(void* plan, const float* pcm, int64_t pcm_len, const aa
     if (fe_fast4096(*p)) {                                                                              \
         rc = launch_stft4096<PM>(*p, pcm, windows, n_win, ws.stats, ws.melS, ws.blkmax, st);            \
     } else switch (p->cfg.n_fft) {                                                                      \
+        case 256: rc = launch_stft_small<256, PM>(*p, pcm, windows, n_win, ws.stats, ws.melS, ws.blkmax, st); break;   \
+        case 512: rc = launch_stft_small<512, PM>(*p, pcm, windows, n_win, ws.stats, ws.melS, ws.blkmax, st); break;   \
+        case 1024: rc = launch_stft_small<1024, PM>(*p, pcm, windows, n_win, ws.stats, ws.melS, ws.blkmax, st); break; \
         case 2048: rc = launch_stft<2048, PM>(*p, pcm, windows, n_win, ws.stats, ws.melS, ws.blkmax, st); break; \
         case 4096: rc = launch_stft<4096, PM>(*p, pcm, windows, n_win, ws.stats, ws.melS, ws.blkmax, st); break; \
         default: rc = launch_stft<8192, PM>(*p, pcm, windows, n_win, ws.stats, ws.melS, ws.blkmax, st); break;   \
@@ -1262,7 +1600,7 @@ extern "C" int aa_fe_stage_info(const void* plan, int32_t stage, char* name, int
     switch (stage) {
         case FE_STAGE_STATS: nm = "fe_stats"; fl = 2 * L; by = 4 * L; break;
         case FE_STAGE_STFT:
-            nm = fe_fast4096(*p) ? "fe_stft_mel_4096" : "fe_stft_mel";
+            nm = fe_small(*p) ? "fe_stft_mel_small" : fe_fast4096(*p) ? "fe_stft_mel_4096" : "fe_stft_mel";
             fl = T * (2.5 * N * std::log2(N) + N + 3 * (N / 2 + 1) + 2.0 * p->nnz) + 5 * L;
             by = 4 * L + 4 * M * T;
             break;

@@ -69,7 +69,7 @@ typedef struct aa_window {
  * src/identify_tracks.py:466-497). */
 typedef struct aa_fe_config {
     int32_t win_len;   /* samples per window: int(sr * segment_length) */
-    int32_t n_fft;     /* power of two, 1024..8192 */
+    int32_t n_fft;     /* power of two, 256..8192 */
     int32_t hop;       /* hop_length */
     int32_t n_mels;    /* rows of the filterbank */
     int32_t normalize; /* normalize_data before the STFT */
@@ -92,7 +92,10 @@ const char* aa_last_error(void);
 
 /* ---------------- front end: PCM windows -> log-mel ---------------- */
 /* melfb: host float32 [n_mels][n_fft/2 + 1] dense filterbank (custommel.mel_f
- * or the Slaney filterbank); stored on the device in CSR form. */
+ * or the Slaney filterbank); stored on the device in CSR form.
+ * cfg->n_fft: 256, 512, 1024, 2048, 4096 or 8192; any other value is
+ * AA_ERR_UNSUPPORTED before any device call.  256..1024 take any hop; from
+ * 2048 up a hop whose six-frame span does not fit the LDS is refused. */
 int aa_fe_create(const aa_fe_config* cfg, const float* melfb, void** plan);
 int aa_fe_destroy(void* plan);
 /* frames per window T = 1 + win_len / hop */
