@@ -66,6 +66,15 @@ class FeConfig(C.Structure):
     ]
 
 
+# aa_fe_kernel (include/aa.h): the stft launch a front-end plan chose
+AA_FE_K = {"fe_stft_mel_small": 0, "fe_stft_mel_4096": 1, "fe_stft_mel": 2}
+
+
+class FeInfo(C.Structure):
+    _fields_ = [("kernel", C.c_int32), ("T", C.c_int32), ("kmin", C.c_int32), ("kmax", C.c_int32),
+                ("nnz", C.c_int32), ("nparts", C.c_int32), ("lds_bytes", C.c_int64), ("grid", C.c_int32)]
+
+
 class Layer(C.Structure):
     _fields_ = [
         ("op", C.c_int32), ("kh", C.c_int32), ("kw", C.c_int32), ("filters", C.c_int32),
@@ -242,6 +251,9 @@ _SIGS = {
     "aa_fe_set_timing": (C.c_int, [C.c_void_p, C.c_uint32]),
     "aa_fe_stage_time": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_double),
                                    C.POINTER(C.c_int64)]),
+    "aa_fe_plan": (C.c_int, [C.POINTER(FeConfig), C.c_void_p, C.POINTER(C.c_void_p)]),
+    "aa_fe_plan_info": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(FeInfo)]),
+    "aa_fe_plan_image": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "aa_model_create": (C.c_int, [C.POINTER(Layer), C.c_int32, C.c_void_p, C.c_int64, C.c_int32,
                                   C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
     "aa_model_destroy": (C.c_int, [C.c_void_p]),

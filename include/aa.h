@@ -108,13 +108,44 @@ size_t aa_fe_workspace_bytes(const void* plan, int32_t max_windows);
 int aa_fe_run(void* plan, const float* pcm, int64_t pcm_len, const aa_window* windows,
               int32_t n_win, void* out, int32_t* win_status, void* workspace,
               size_t workspace_bytes, void* stream);
-/* Launch stages of aa_fe_run (0 fe_stats, 1 fe_stft_mel, 2 fe_db) and their
- * timing, same contract as aa_model_stage_* below. */
+/* Launch stages of aa_fe_run and their timing, same contract as
+ * aa_model_stage_* below: 0 fe_stats, 2 fe_db (csrc/aa_frontend.hip), 1 the
+ * stft + mel kernel the plan chose (csrc/aa_fe_plan.h choose_kernel; its name
+ * is stage_info's): fe_stft_mel_small at n_fft 256..1024, fe_stft_mel from
+ * 2048 up (both csrc/aa_fe_stft.h), fe_stft_mel_4096 at n_fft 4096 with the
+ * kept band inside X[2..1022] (csrc/aa_fe_wave4096.h). */
 int aa_fe_n_stages(const void* plan);
 int aa_fe_stage_info(const void* plan, int32_t stage, char* name, int32_t name_len,
                      double* flops_per_item, double* bytes_per_item);
 int aa_fe_set_timing(void* plan, uint32_t stage_mask);
 int aa_fe_stage_time(void* plan, int32_t stage, double* total_ms, int64_t* count);
+
+/* The plan alone, on the host (the aa_model_plan contract): aa_fe_create's
+ * arguments, checks, return codes and aa_last_error texts, but no device
+ * memory and no HIP call.  aa_fe_n_frames / workspace_bytes / n_stages /
+ * stage_info / destroy serve a planned plan; aa_fe_run, aa_fe_set_timing and
+ * aa_fe_stage_time return AA_ERR_INVALID. */
+typedef enum aa_fe_kernel { AA_FE_K_SMALL = 0, AA_FE_K_WAVE4096 = 1, AA_FE_K_GENERIC = 2 } aa_fe_kernel;
+typedef struct aa_fe_info {
+    int32_t kernel;    /* aa_fe_kernel: the stft launch (stage 1) */
+    int32_t T;         /* frames per window */
+    int32_t kmin;      /* first and last filterbank bin with a nonzero weight */
+    int32_t kmax;      /* (0, 0 for an all-zero filterbank) */
+    int32_t nnz;       /* CSR values */
+    int32_t nparts;    /* per-window partial maxima that fe_db reads */
+    int64_t lds_bytes; /* dynamic LDS of the stft launch */
+    int32_t grid;      /* its blocks for n_win windows */
+} aa_fe_info;
+int aa_fe_plan(const aa_fe_config* cfg, const float* melfb, void** plan);
+int aa_fe_plan_info(const void* plan, int32_t n_win, aa_fe_info* out);
+/* The bytes aa_fe_create would upload (the aa_model_stage_image contract: *len
+ * the image's bytes; buf NULL: size query; AA_ERR_INVALID when cap < *len;
+ * planned plans only, a created one has released them: AA_ERR_UNSUPPORTED).
+ * which = 0 the periodic Hann f32 [n_fft], 1 tw = exp(-2 pi i m / (n_fft/2))
+ * float2 [n_fft/2], 2 tw2 = exp(-2 pi i k / n_fft) float2 [n_fft/2 + 1], 3 the
+ * CSR rows int32x4 [n_mels] (first bin, count, value offset, 0), 4 the CSR
+ * values f32, 5 fe_stft_mel_4096's image (len 0 unless n_fft is 4096). */
+int aa_fe_plan_image(const void* plan, int32_t which, void* buf, size_t cap, size_t* len);
 
 /* ---------------- CNN: log-mel windows -> logits / probabilities ---------------- */
 /* Supported layer sequences: [MagTransform] then Conv2D blocks (Conv2D

@@ -4,7 +4,12 @@ Tolerance (stated, fp32): log-mel |delta| <= 1e-3 dB.  The reference computes
 the STFT in float64 (librosa 0.11 + numpy pocketfft) and stores complex64;
 the GPU transform is float32 throughout, so its error is ~1e-5 dB on noise-like
 audio and ~6e-4 dB in the worst bands of a pure tone next to the -80 dB floor
-(measured with a float32 pocketfft at the same configuration).  Non-dB outputs
+(measured with a float32 pocketfft at the same configuration).  For the inputs
+of test_generic_kernel_large_sizes a float32 FFT (scipy.fft.rfft on float32
+frames, float32 mel sums) differs from the oracle by 1.1e-5 dB (full view) and
+2.1e-4 dB (short view, whose zero-padded frames reach the -80 dB floor) at
+n_fft 4096 with the full band, and by 7.6e-6 dB and 2.5e-4 dB at n_fft 8192: a
+quarter of the gate at most.  Non-dB outputs
 (power mel) compare with rtol 2e-4 relative to the window maximum.
 """
 import numpy as np
@@ -76,6 +81,38 @@ def test_frontend_matches_oracle(gpu, name):
         else:
             scale = np.abs(ref).max()
             assert np.abs(g - ref).max() <= 2e-4 * scale, (name, i)
+
+
+# Two instantiations of fe_stft_mel that no other case reaches, on half-second
+# windows (38 and 24 frames: a few 6-frame items per window, the first ones of a
+# view that starts inside the window with a partial segment).
+NEW_CASES = {
+    "nfft4096_fullband": dict(htk=True, segment_length=0.5, fmin=0, fmax=24000),  # band outside X[2..1022]
+    "nfft8192": dict(htk=True, segment_length=0.5, n_fft=8192, hop_length=1024),
+}
+# one full view; one short view whose left padding and centre padding meet in
+# the first frames
+NEW_VIEWS = [(0, 24000, 0), (30000, 9000, 1500)]
+
+
+@pytest.mark.parametrize("name", list(NEW_CASES))
+def test_generic_kernel_large_sizes(gpu, name):
+    """fe_stft_mel<4096> (the fallback of n_fft 4096 when the kept band leaves
+    X[2..1022]) and fe_stft_mel<8192> against the oracle at DB_TOL (the float32
+    reference's own error for these inputs: module docstring)."""
+    from aa_amd.frontend import FeSettings, FrontEnd
+    s = FeSettings(**NEW_CASES[name])
+    assert s.n_frames == {"nfft4096_fullband": 38, "nfft8192": 24}[name]
+    assert FrontEnd(s).stage_info(1)[0] == "fe_stft_mel"
+    clip = synth.clip(3, seconds=1.0)
+    got, status = _setup(s, clip, NEW_VIEWS)
+    assert (status == 0).all()
+    for i, v in enumerate(NEW_VIEWS):
+        ref = fe_oracle.window_logmel(_raw_window(clip, v, s.win_len), _cfg(s))
+        assert got[i].shape == ref.shape
+        err = np.abs(got[i] - ref).max()
+        print(name, v, "max |delta| dB", err)
+        assert err <= DB_TOL, (name, i, err)
 
 
 def test_pure_tone_near_floor(gpu):

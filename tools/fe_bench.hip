@@ -14,13 +14,11 @@ using namespace aa;
 template <int DIAG>
 static float time_diag(const FePlan& p, const float* pcm, const aa_window* wins, int n_win, const float4* stats,
                        float* melS, float* blkmax, int iters) {
-    const size_t lds = fe_lds_bytes4096(p);
+    const size_t lds = p.lds_bytes;
     (void)hipFuncSetAttribute((const void*)fe_stft_mel_4096<PM_SQUARE, DIAG>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     const int n_frames = p.T * n_win;
-    const int per_cu = std::max(1, std::min(2, (int)((160 * 1024) / lds)));
-    int grid = std::min((n_frames + kWpb - 1) / kWpb, 256 * per_cu);
-    grid = (grid + 7) & ~7;
+    const int grid = p.grid(n_win);
     auto go = [&]() {
         hipLaunchKernelGGL((fe_stft_mel_4096<PM_SQUARE, DIAG>), dim3(grid), dim3(64 * kWpb), lds, 0, pcm, wins,
                            stats, p.d_tw, p.d_tw2, p.d_cimg, p.cimg_bytes, p.cfg.win_len, p.cfg.hop, p.T,
@@ -54,7 +52,9 @@ int main(int argc, char** argv) {
     void* plan = nullptr;
     if (aa_fe_create(&cfg, fb.data(), &plan) != AA_OK) { printf("create: %s\n", aa_last_error()); return 1; }
     const FePlan& p = *static_cast<FePlan*>(plan);
-    printf("nnz %d kmin %d kmax %d fast %d lds %zu\n", p.nnz, p.kmin, p.kmax, (int)fe_fast4096(p), fe_lds_bytes4096(p));
+    printf("nnz %d kmin %d kmax %d fast %d lds %zu\n", p.nnz, p.kmin, p.kmax, (int)(p.kernel == FE_K_WAVE4096), p.lds_bytes);
+    // the plan's LDS bytes and grid are those of the kernel it chose
+    if (p.kernel != FE_K_WAVE4096) { printf("the plan did not choose fe_stft_mel_4096\n"); return 1; }
     const size_t n_pcm = 2 * 2880000;
     std::vector<float> h(n_pcm);
     uint32_t rs = 12345u;  // a local generator: the HIP runtime draws on rand() itself
@@ -71,16 +71,14 @@ int main(int argc, char** argv) {
     (void)hipMalloc(&wins, n_win * sizeof(aa_window));
     (void)hipMalloc(&stats, n_win * kStatSplit * sizeof(float4));
     (void)hipMalloc(&melS, (size_t)n_win * n_mels * p.T * 4);
-    (void)hipMalloc(&blkmax, (size_t)n_win * p.nfblk * 4);
+    (void)hipMalloc(&blkmax, (size_t)n_win * p.nparts * 4);
     (void)hipMemcpy(pcm, h.data(), n_pcm * 4, hipMemcpyHostToDevice);
     (void)hipMemcpy(wins, hw.data(), n_win * sizeof(aa_window), hipMemcpyHostToDevice);
     hipLaunchKernelGGL(fe_stats, dim3(kStatSplit, n_win), dim3(256), 0, 0, pcm, wins, cfg.win_len, stats);
     const int it = 20;
 #define T_(D) printf("DIAG %3d: %7.1f us\n", D, time_diag<D>(p, pcm, wins, n_win, stats, melS, blkmax, it));
     if (argc > 1 && std::string(argv[1]) == "stamps") {  // per-phase s_memtime totals (DIAG 128)
-        const int per_cu = std::max(1, std::min(2, (int)((160 * 1024) / fe_lds_bytes4096(p))));
-        int grid = std::min((p.T * n_win + kWpb - 1) / kWpb, 256 * per_cu);
-        grid = (grid + 7) & ~7;
+        const int grid = p.grid(n_win);
         const size_t nw = (size_t)grid * kWpb;
         unsigned long long* d_st;
         (void)hipMalloc(&d_st, nw * kFeStampPh * 64 * 8);
