@@ -67,7 +67,7 @@ class FeConfig(C.Structure):
 
 
 # aa_fe_kernel (include/aa.h): the stft launch a front-end plan chose
-AA_FE_K = {"fe_stft_mel_small": 0, "fe_stft_mel_4096": 1, "fe_stft_mel": 2}
+AA_FE_K = {"fe_stft_mel_small": 0, "fe_stft_mel_4096": 1, "fe_stft_mel": 2, "fe_stft_mel_mixed": 3}
 
 
 class FeInfo(C.Structure):
@@ -254,6 +254,7 @@ _SIGS = {
     "aa_fe_plan": (C.c_int, [C.POINTER(FeConfig), C.c_void_p, C.POINTER(C.c_void_p)]),
     "aa_fe_plan_info": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(FeInfo)]),
     "aa_fe_plan_image": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "aa_fe_plan_passes": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32)]),
     "aa_model_create": (C.c_int, [C.POINTER(Layer), C.c_int32, C.c_void_p, C.c_int64, C.c_int32,
                                   C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
     "aa_model_destroy": (C.c_int, [C.c_void_p]),

@@ -5,7 +5,7 @@ group configures it, src/identify_tracks.py:465-497).  ``run`` takes the whole
 recording resident on the device plus a device table of window views and
 returns ``[n_win, n_mels, T, channels]`` float32 -- the stack of what
 ``get_spect`` returns per window (src/identify_tracks.py:212-288).
-``n_fft`` is a power of two from 256 to 8192 (aa_fe_create refuses the rest).
+``n_fft``: see ``FeSettings``.
 """
 from __future__ import annotations
 
@@ -20,6 +20,11 @@ from . import _lib, melbank
 
 @dataclass(frozen=True)
 class FeSettings:
+    """``n_fft`` lies in 256..8192 and is a power of two, or a multiple of 16
+    whose sixteenth has no prime factor but 2, 3 and 5 (4800 = sr // 10, the
+    25 / 50 ms windows 1200 / 2400, 960, 1920, 400, 800, 1600, ...);
+    aa_fe_create refuses the rest (odd sizes, 1000 and 3000, which are 8 mod
+    16, a factor 7 or larger such as 4410)."""
     sr: int = 48000
     segment_length: float = 3
     n_fft: int = 4096

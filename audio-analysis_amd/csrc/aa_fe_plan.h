@@ -3,9 +3,9 @@
 // can be made and inspected on a machine without a GPU (aa_fe_plan /
 // aa_fe_plan_info / aa_fe_plan_image).  aa_fe_create uploads the images and
 // releases them; aa_fe_run launches what was chosen here.
-// The LDS layouts of fe_stft_mel and fe_stft_mel_small are stated here once
-// (FeLdsGeneric, FeLdsSmall): the kernel steps its pointers through the
-// regions, the planner adds them up.
+// The LDS layouts of fe_stft_mel, fe_stft_mel_mixed and fe_stft_mel_small are
+// stated here once (FeLdsGeneric, FeLdsSmall): the kernel steps its pointers
+// through the regions, the planner adds them up.
 #pragma once
 
 #include <algorithm>
@@ -39,12 +39,15 @@ __host__ __device__ constexpr int fe_mel_slots(int n_mels) { return (n_mels + 63
 // ---- LDS layouts: the regions of the dynamic LDS in order, each with its length in its
 // own element type.  The kernel steps its pointers through them, bytes() adds them up. ----
 // fe_stft_mel: segment (float) | bufA, bufB (float2) | melT [n_mels][kFpb] (float) | CSR rows (int4) | values (float)
+// fe_stft_mel_mixed: the same, with its copy of the tw table (float2, n_fft/2 entries, or none) after bufB
 struct FeLdsGeneric {
-    int seg, buf, melT, rows, vals;
-    __host__ __device__ FeLdsGeneric(int n_fft, int hop, int n_mels, int nnz)
-        : seg(((kFpb - 1) * hop + n_fft + 3) & ~3), buf(n_fft / 2 + n_fft / 16), melT((n_mels * kFpb + 3) & ~3),
-          rows(n_mels), vals(nnz > 1 ? nnz : 1) {}
-    size_t bytes() const { return 4 * ((size_t)seg + 4 * (size_t)buf + melT + 4 * (size_t)rows + vals); }
+    int seg, buf, tw, melT, rows, vals;
+    __host__ __device__ FeLdsGeneric(int n_fft, int hop, int n_mels, int nnz, int tw_entries = 0)
+        : seg(((kFpb - 1) * hop + n_fft + 3) & ~3), buf(n_fft / 2 + n_fft / 16), tw(tw_entries),
+          melT((n_mels * kFpb + 3) & ~3), rows(n_mels), vals(nnz > 1 ? nnz : 1) {}
+    size_t bytes() const {
+        return 4 * ((size_t)seg + 4 * (size_t)buf + 2 * (size_t)tw + melT + 4 * (size_t)rows + vals);
+    }
 };
 // fe_stft_mel_small (no term in the hop): even, odd samples (float) | wave buffers (float2) | CSR rows (int4) | values
 struct FeLdsSmall {
@@ -55,7 +58,43 @@ struct FeLdsSmall {
 // fe_stft_mel_4096, in bytes: CSR image (rows | values, as uploaded) | a kHalf-float2 buffer per wave
 static inline size_t fe_lds_bytes4096(int cimg_bytes) { return (size_t)cimg_bytes + sizeof(float2) * (size_t)kWpb * kHalf; }
 
-enum FeKernel { FE_K_SMALL = AA_FE_K_SMALL, FE_K_WAVE4096 = AA_FE_K_WAVE4096, FE_K_GENERIC = AA_FE_K_GENERIC };
+enum FeKernel {
+    FE_K_SMALL = AA_FE_K_SMALL, FE_K_WAVE4096 = AA_FE_K_WAVE4096, FE_K_GENERIC = AA_FE_K_GENERIC,
+    FE_K_MIXED = AA_FE_K_MIXED
+};
+
+constexpr int kMaxPasses = 8;  // Stockham passes of a schedule (7 at n_fft 7776 = 2 * 8 * 2 * 3^5)
+
+// threads of an fe_stft_mel_mixed block: a thread per radix-8 butterfly of pass 1, in whole waves
+__host__ __device__ constexpr int fe_mixed_threads(int n_fft) { return (n_fft / 16 + 63) / 64 * 64; }
+
+// n_fft of fe_stft_mel_mixed: a multiple of 16 whose sixteenth has no prime factor but 2, 3 and 5
+static bool fe_smooth16(int n) {
+    if (n <= 0 || n % 16) return false;
+    int m = n / 16;
+    for (int f : {2, 3, 5})
+        while (m % f == 0) m /= f;
+    return m == 1;
+}
+
+// Pass schedule of the NC = n_fft/2 point transform of fe_stft_mel_mixed: radices r_1 .. r_P with
+// product NC, in this fixed order: the radix 8 of pass 1 (from the samples), every further 8, the
+// 5s, one 4, the 3s, one 2 (NC/8 = 2^a 3^b 5^c: a/3 eights, a 4 when a % 3 == 2, a 2 when
+// a % 3 == 1).  The sub-transform size before a pass, NS = the product of the earlier radices, is
+// a multiple of 8 from pass 2 on.  Returns P (<= kMaxPasses inside 256..8192).
+static int fe_mixed_schedule(int n_fft, int* radix) {
+    int m = n_fft / 16, a = 0, b = 0, c = 0, n = 0;
+    while (m % 2 == 0) { m /= 2; ++a; }
+    while (m % 3 == 0) { m /= 3; ++b; }
+    while (m % 5 == 0) { m /= 5; ++c; }
+    radix[n++] = 8;
+    for (int i = 0; i < a / 3; ++i) radix[n++] = 8;
+    for (int i = 0; i < c; ++i) radix[n++] = 5;
+    if (a % 3 == 2) radix[n++] = 4;
+    for (int i = 0; i < b; ++i) radix[n++] = 3;
+    if (a % 3 == 1) radix[n++] = 2;
+    return n;
+}
 
 struct FePlan {
     aa_fe_config cfg;
@@ -67,6 +106,9 @@ struct FePlan {
     int nparts = 0;    // per-window partial maxima that fe_db reads
     int per_cu = 1;    // blocks resident together on a CU
     size_t lds_bytes = 0;  // dynamic LDS of the chosen kernel
+    int n_pass = 0;    // Stockham passes of the chosen kernel and their radices (aa_fe_plan_passes);
+    int radix[kMaxPasses] = {};  // FE_K_MIXED runs this schedule, the others have it built in
+    bool tw_lds = false;  // FE_K_MIXED: the block keeps a copy of tw in LDS (it fits the bound)
     // host images, released once aa_fe_create has uploaded them
     std::vector<float> h_win;    // periodic Hann, f32 [n_fft]
     std::vector<float2> h_tw;    // exp(-2 pi i m / Nc), m < Nc
@@ -93,7 +135,9 @@ struct FePlan {
 // kernel covers n_fft 4096 whenever the kept band fits the per-wave buffer (15 bins per lane):
 // inside X[2..1022] (Hann neighbours in range and clear of the bins -1..1 that the folded
 // normalisation offset touches), padded rows (+3 bins) inside the 15 x 64 power slots.
+// Every accepted n_fft that is not a power of two runs fe_stft_mel_mixed.
 static FeKernel choose_kernel(int n_fft, int kmin, int kmax) {
+    if (n_fft & (n_fft - 1)) return FE_K_MIXED;
     if (n_fft <= 1024) return FE_K_SMALL;
     const bool wave = n_fft == 4096 && kmin >= 2 && kmax <= 1022 && kmin + 64 * (kHalf / 64 - 1) < kHalf &&
                       kmax - kmin + 1 + 3 <= (kHalf / 64 - 1) * 64;
@@ -101,7 +145,8 @@ static FeKernel choose_kernel(int n_fft, int kmin, int kmax) {
 }
 
 static const char* fe_kernel_name(FeKernel k) {
-    return k == FE_K_SMALL ? "fe_stft_mel_small" : k == FE_K_WAVE4096 ? "fe_stft_mel_4096" : "fe_stft_mel";
+    return k == FE_K_SMALL ? "fe_stft_mel_small" : k == FE_K_WAVE4096 ? "fe_stft_mel_4096"
+           : k == FE_K_MIXED ? "fe_stft_mel_mixed" : "fe_stft_mel";
 }
 
 // CSR image of the wave-per-frame kernel, byte-identical to its LDS
@@ -145,8 +190,9 @@ static std::vector<char> fe_cimg4096(const std::vector<int4>& rows, const std::v
 static int plan_fe(const aa_fe_config* cfg, const float* melfb, FePlan* p) {
     AA_CHECK(cfg && melfb && p, AA_ERR_INVALID, "aa_fe_create: null argument");
     const int n = cfg->n_fft;
-    AA_CHECK(n >= 256 && n <= 8192 && (n & (n - 1)) == 0, AA_ERR_UNSUPPORTED,
-             "aa_fe_create: n_fft %d not supported (power of two 256..8192)", n);
+    AA_CHECK(n >= 256 && n <= 8192 && ((n & (n - 1)) == 0 || fe_smooth16(n)), AA_ERR_UNSUPPORTED,
+             "aa_fe_create: n_fft %d not supported (power of two, or a multiple of 16 with factors 2, 3, 5, 256..8192)",
+             n);
     AA_CHECK(cfg->hop > 0 && cfg->win_len > 0 && cfg->n_mels > 0 && cfg->channels >= 1 &&
                  (cfg->out_f16 == 0 || cfg->out_f16 == 1),
              AA_ERR_INVALID, "aa_fe_create: bad sizes");
@@ -181,8 +227,16 @@ static int plan_fe(const aa_fe_config* cfg, const float* melfb, FePlan* p) {
     // (from 2048 up the hop is held to fe_stft_mel's segment whichever kernel runs; fe_stft_mel_small
     // takes any hop: past its shared span, frames load their own samples.  FE_K_WAVE4096's own bytes are
     // not bounded here: a dense filterbank can pass this and be refused at launch, launch_stft.)
-    const size_t lds_generic = FeLdsGeneric(n, cfg->hop, cfg->n_mels, p->nnz).bytes();
+    size_t lds_generic = FeLdsGeneric(n, cfg->hop, cfg->n_mels, p->nnz).bytes();
     const size_t lds_small = FeLdsSmall(cfg->n_mels, p->nnz).bytes();
+    if (p->kernel == FE_K_MIXED) {
+        // fe_stft_mel_mixed reads its pass twiddles from the tw table: from a copy in LDS when the
+        // layout with it stays inside the bound, from global memory otherwise (the long transforms
+        // at long hops: 7680 / 1024 / 160 bands is 141 KB without the 30 KB copy)
+        const size_t with_tw = FeLdsGeneric(n, cfg->hop, cfg->n_mels, p->nnz, n / 2).bytes();
+        p->tw_lds = with_tw <= 150 * 1024;
+        if (p->tw_lds) lds_generic = with_tw;
+    }
     if (p->kernel == FE_K_SMALL)
         AA_CHECK(lds_small <= 160 * 1024, AA_ERR_UNSUPPORTED,
                  "aa_fe_create: filterbank (%d bands, %d weights) too large for the LDS", cfg->n_mels, p->nnz);
@@ -203,6 +257,13 @@ static int plan_fe(const aa_fe_config* cfg, const float* melfb, FePlan* p) {
     // at most 2 (1 measured -1.5 % on the two-stream step, profiles/r05/ab_fe_per_cu.txt)
     p->per_cu = std::max(1, wave ? std::min(2, (int)((160 * 1024) / p->lds_bytes))
                                  : (int)((160 * 1024) / (p->lds_bytes + 256)));
+
+    // the passes: fe_stft_mel_mixed's schedule; the built-in ones of the other kernels (fe_stft_mel_4096:
+    // its two register DFT-32s as 8 x 4 each, then the radix 2 across the lane pair)
+    if (p->kernel == FE_K_MIXED) p->n_pass = fe_mixed_schedule(n, p->radix);
+    else if (wave) { const int r[5] = {8, 4, 8, 4, 2}; std::copy(r, r + 5, p->radix); p->n_pass = 5; }
+    else if (small) { const int r[3] = {8, 8, n / 128}; std::copy(r, r + 3, p->radix); p->n_pass = 3; }
+    else { const int r[4] = {8, 8, 8, n / 1024}; std::copy(r, r + 4, p->radix); p->n_pass = 4; }
 
     const int nc = n / 2;
     p->h_win.resize(n);

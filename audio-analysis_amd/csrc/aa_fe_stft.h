@@ -1,6 +1,7 @@
-// The two LDS Stockham STFT + mel kernels of the front end, fe_stft_mel (n_fft
-// 2048..8192) and fe_stft_mel_small (256..1024), and the device helpers they
-// share.  Included by aa_frontend.hip; LDS layouts and constants: aa_fe_plan.h.
+// The three LDS Stockham STFT + mel kernels of the front end, fe_stft_mel (n_fft
+// 2048..8192), fe_stft_mel_small (256..1024) and fe_stft_mel_mixed (the sizes
+// that are no powers of two), and the device helpers they share.  Included by
+// aa_frontend.hip; LDS layouts and constants: aa_fe_plan.h.
 #pragma once
 
 #include "aa_fe_plan.h"
@@ -556,6 +557,262 @@ __global__ __launch_bounds__(64 * kSmallWaves, 3) void fe_stft_mel_small(
         }
         bmax = wave_max(bmax);
         if (lane == 0) blkmax[(size_t)w * nblk * kSmallWaves + fb * kSmallWaves + wv] = bmax;
+    }  // item loop
+}
+
+// ---------------------------------------------------------------------------
+// fe_stft_mel_mixed: every accepted n_fft that is not a power of two (a
+// multiple of 16 with n_fft / 16 = 2^a 3^b 5^c: 400 .. 7776) -- fe_stft_mel's
+// contract, arguments, item loop, staging, real split and mel rows, with the
+// transform's passes taken from the plan (fe_mixed_schedule, aa_fe_plan.h)
+// instead of from the template: `sched` holds the radices, 4 bits each, first
+// pass lowest, 0 past the last.  Pass 1 is the radix 8 from the windowed
+// samples; every later pass is MixedPass<R>::run, picked by a switch on the
+// radix that is uniform over the block.
+//
+// NC and the passes' NB differ per size and are no multiples of the block, so
+//   * the block is fe_mixed_threads() = NC/8 rounded up to whole waves (64 ..
+//     512); the threads past NC/8 take no butterfly of pass 1,
+//   * every pass loops j = tid; j < NB; j += NT, and every thread reaches
+//     every __syncthreads().
+// Twiddles: the schedule is a runtime value, so there are no per-size register
+// sets; pass twiddles are read per butterfly from the tw table, whose entries
+// are correctly rounded (no products of twiddles).  TWL: the block copies tw
+// into LDS once (plan_fe: whenever the layout with the copy keeps the 150 KB
+// bound); otherwise the reads go to global memory (L1/L2: the table is at most
+// 31 KB and shared by every block).
+//
+// LDS banks, NB and NS being multiples of 8 but not powers of two (r = 3, 5):
+//   reads   lane j reads pidx(j) + q (NB + NB/8): for one q the 32 lanes of a
+//           half-wave read 32 consecutive points across 4 pads, 36 float2
+//           slots over 32 (ds_read_b64: slot mod 32 per half-wave): 4 lanes
+//           share a bank 2-way, whatever NB is.
+//   writes  16-lane groups, slot mod 16.  NS a multiple of 16: one run of 16
+//           consecutive points across 2 pads, 2 lanes 2-way.  NS = 8 mod 16
+//           (8, 24, 40, 120, ...): two runs of 8, the second 9 (NS r - NS)/8
+//           + 9 slots on: the runs overlap in 8 - (9 NS r / 8 mod 16) banks at
+//           most, 2-way (r = 8 at NS = 8: 72 = 8 mod 16, conflict-free; r = 5:
+//           45 -> 5 lanes; r = 3: 27 -> 3 lanes).  Nothing is worse than 2-way.
+//   tw      (TWL) lane k reads entry q k NC/(NS r): stride 1 in the last pass,
+//           the product of the later radices before; the odd factors sit late
+//           in the schedule, so the early strides are odd multiples of a small
+//           power of two (4800: 60, 12, 3, 1) and spread over the banks.
+// None of this has been measured with counters.
+// ---------------------------------------------------------------------------
+template <int R>
+struct MixedPass {
+    // Pass::run's indexing with runtime NC, NS: butterfly j < NB = NC/R reads src[pidx(j + q NB)],
+    // multiplies by tw[q k NC/(NS R)], k = j % NS, and writes dst[pidx((j / NS) NS R + k + q NS)].
+    // The exponent q k NC/(NS R) <= (R - 1)(NS - 1) NB/NS < NC needs no reduction mod NC (the
+    // power-of-two kernels' & (NC - 1) never acts either).
+    __device__ __forceinline__ static void run(const float2* __restrict__ src, float2* __restrict__ dst,
+                                               const float2* __restrict__ twp, int NC, int NS, int tid, int NT) {
+        const int NB = NC / R;
+        const int ts = NB / NS;                  // twiddle stride NC / (NS R)
+        const float inv_ns = 1.0f / (float)NS;   // j / NS as a float product: exact below 2^21
+        for (int j = tid; j < NB; j += NT) {
+            const int blk = (int)(((float)j + 0.5f) * inv_ns), k = j - blk * NS;
+            // NB and NS are multiples of 8: pidx(i + 8c) = pidx(i) + 9c
+            const float2* s0 = src + pidx(j);
+            float2 v[R], t[R - 1];
+#pragma unroll
+            for (int q = 1; q < R; ++q) t[q - 1] = twp[q * k * ts];
+#pragma unroll
+            for (int q = 0; q < R; ++q) v[q] = s0[q * (NB + NB / 8)];
+#pragma unroll
+            for (int q = 1; q < R; ++q) v[q] = cmul(v[q], t[q - 1]);
+            if constexpr (R == 8) dft8(v);
+            if constexpr (R == 5) dft5(v);
+            if constexpr (R == 4) dft4(v[0], v[1], v[2], v[3]);
+            if constexpr (R == 3) dft3(v[0], v[1], v[2]);
+            if constexpr (R == 2) dft2(v[0], v[1]);
+            float2* d0 = dst + pidx(blk * NS * R + k);
+#pragma unroll
+            for (int q = 0; q < R; ++q) d0[q * (NS + NS / 8)] = v[q];
+        }
+    }
+};
+
+template <int PM, bool TWL>
+__global__ __launch_bounds__(512) void fe_stft_mel_mixed(
+    const float* __restrict__ pcm, const aa_window* __restrict__ wins, const float4* __restrict__ stats,
+    const float* __restrict__ hann, const float2* __restrict__ tw, const float2* __restrict__ tw2,
+    const int4* __restrict__ rows, const float* __restrict__ vals, int nnz, int win_len, int hop, int T,
+    int n_mels, int kmin, int kmax, int normalize, float power, int nblk, int n_items,
+    float* __restrict__ melS, float* __restrict__ blkmax, int n_fft, unsigned sched) {
+    const int NC = n_fft / 2;
+    const int N8 = NC / 8;                 // butterflies of pass 1
+    const int NT = blockDim.x;             // fe_mixed_threads(n_fft) >= N8
+    constexpr int KREG = 4;  // post-processing bins per thread with register twiddles
+    extern __shared__ float lds[];
+    const FeLdsGeneric L(n_fft, hop, n_mels, nnz, TWL ? NC : 0);
+    float* seg = lds;
+    float2* bufA = reinterpret_cast<float2*>(seg + L.seg);
+    float2* bufB = bufA + L.buf;
+    float2* stw = bufB + L.buf;            // the block's copy of tw (TWL)
+    float* melT = reinterpret_cast<float*>(stw + L.tw);  // [n_mels][kFpb] staging
+    int4* srows = reinterpret_cast<int4*>(melT + L.melT);
+    float* svals = reinterpret_cast<float*>(srows + L.rows);
+
+    // --- per-thread constants, loaded once per block ---
+    const int tid = threadIdx.x;
+    const bool p1 = tid < N8;              // the thread has a butterfly in pass 1
+    float hw[8][2];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+        const int n = min(tid, N8 - 1) + r * N8;
+        const float2 h = reinterpret_cast<const float2*>(hann)[n];
+        hw[r][0] = h.x;
+        hw[r][1] = h.y;
+    }
+    float2 w2r[KREG];
+#pragma unroll
+    for (int i = 0; i < KREG; ++i) {
+        w2r[i] = tw2[min(kmin + tid + i * NT, kmax)];
+    }
+    if constexpr (TWL)
+        for (int i = tid; i < NC; i += NT) stw[i] = tw[i];
+    const float2* twp = TWL ? stw : tw;
+    for (int i = tid; i < n_mels; i += NT) srows[i] = rows[i];
+    for (int i = tid; i < nnz; i += NT) svals[i] = vals[i];
+
+    __syncthreads();
+    // persistent loop over (window, frame block) items
+    for (int item = blockIdx.x; item < n_items; item += gridDim.x) {
+    const int w = item / nblk;
+    const int fb = item - w * nblk;
+    const int f0 = fb * kFpb;
+    const int nf = min(kFpb, T - f0);
+    const int seg_len = (nf - 1) * hop + n_fft;
+    // --- normalisation constants (normalize_data, :203-208) ---
+    const aa_window d = wins[w];
+    float lo = INFINITY, hi = -INFINITY;
+#pragma unroll
+    for (int s = 0; s < kStatSplit; ++s) {
+        float4 st = stats[w * kStatSplit + s];
+        lo = fminf(lo, st.x);
+        hi = fmaxf(hi, st.y);
+    }
+    const float scale = __fsub_rn(hi, lo);  // == max(x - min) (monotone rounding)
+    const float inv = __fdiv_rn(1.f, scale);
+
+    // --- overlapped segment -> LDS, normalised; loads issued in batches of
+    // SEGU per thread before any is consumed ---
+    const int base = f0 * hop - n_fft / 2;  // window index of seg[0]
+    constexpr int SEGU = 8;
+    const long long safe = d.n_valid > 0 ? d.src : 0;  // any in-bounds sample
+    for (int q0 = 0; q0 < seg_len; q0 += SEGU * NT) {
+        float raw[SEGU];
+        bool ok[SEGU];
+#pragma unroll
+        for (int u = 0; u < SEGU; ++u) {  // unconditional loads from clamped addresses
+            const int q = q0 + u * NT + tid;
+            const int i = base + q;
+            const int rel = i - d.pad_left;
+            ok[u] = q < seg_len && i >= 0 && i < win_len && rel >= 0 && rel < d.n_valid;
+            raw[u] = pcm[ok[u] ? d.src + rel : safe];
+        }
+#pragma unroll
+        for (int u = 0; u < SEGU; ++u) {
+            const int q = q0 + u * NT + tid;
+            const int i = base + q;
+            if (q < seg_len) {
+                float v = 0.f;
+                if (i >= 0 && i < win_len) {
+                    v = ok[u] ? raw[u] : 0.f;
+                    if (normalize) v = normalize_sample(v, lo, scale, inv);
+                }
+                seg[q] = v;
+            }
+        }
+    }
+    __syncthreads();
+
+    float bmax = 0.f;
+    for (int f = 0; f < nf; ++f) {
+        // pass 1 (NS = 1) straight from the segment: z[n] = xw[2n] + i xw[2n+1]
+        if (p1) {
+            const float* x = seg + f * hop;
+            float2 v[8];
+#pragma unroll
+            for (int r = 0; r < 8; ++r) {
+                const int n = tid + r * N8;
+                v[r] = make_float2(x[2 * n] * hw[r][0], x[2 * n + 1] * hw[r][1]);
+            }
+            dft8(v);
+#pragma unroll
+            for (int r = 0; r < 8; ++r) bufA[pidx(tid * 8 + r)] = v[r];
+        }
+        __syncthreads();
+        // the scheduled passes, ping-pong; the result ends in `src`
+        float2 *src = bufA, *dst = bufB;
+        int NS = 8;
+        for (unsigned sc = sched >> 4; sc != 0; sc >>= 4) {
+            const int R = sc & 15;
+            switch (R) {  // uniform over the block
+                case 8: MixedPass<8>::run(src, dst, twp, NC, NS, tid, NT); break;
+                case 5: MixedPass<5>::run(src, dst, twp, NC, NS, tid, NT); break;
+                case 4: MixedPass<4>::run(src, dst, twp, NC, NS, tid, NT); break;
+                case 3: MixedPass<3>::run(src, dst, twp, NC, NS, tid, NT); break;
+                default: MixedPass<2>::run(src, dst, twp, NC, NS, tid, NT); break;
+            }
+            NS *= R;
+            float2* t = src; src = dst; dst = t;
+            __syncthreads();
+        }
+        const float2* Z = src;             // natural order
+        float* Pf = reinterpret_cast<float*>(dst);  // free scratch for |X|^p
+        for (int i = 0; kmin + tid + i * NT <= kmax; ++i) {
+            const int k = kmin + tid + i * NT;
+            float re, im;
+            if (k == 0 || k == NC) {
+                const float2 z0 = Z[0];  // pidx(0) == 0
+                re = (k == 0) ? z0.x + z0.y : z0.x - z0.y;
+                im = 0.f;
+            } else {
+                const float2 a = Z[pidx(k)];
+                const float2 b = Z[pidx(NC - k)];  // conj taken below
+                // E = (a + conj b)/2 ; O = -i (a - conj b)/2 ; X = E + W^k O
+                const float2 E = make_float2(0.5f * (a.x + b.x), 0.5f * (a.y - b.y));
+                const float2 O = make_float2(0.5f * (a.y + b.y), -0.5f * (a.x - b.x));
+                float2 wk;
+                if (i < KREG) {
+                    wk = w2r[0];
+#pragma unroll
+                    for (int q = 1; q < KREG; ++q) if (i == q) wk = w2r[q];
+                } else {
+                    wk = tw2[k];
+                }
+                const float2 X = cadd(E, cmul(wk, O));
+                re = X.x;
+                im = X.y;
+            }
+            Pf[k - kmin] = pow_mag<PM>(re, im, power);
+        }
+        __syncthreads();
+        for (int m = tid; m < n_mels; m += NT) {
+            const int4 rw = srows[m];
+            const float s = mel_row_dot<16>(svals + rw.z, Pf + (rw.x - kmin), rw.y);
+            melT[m * kFpb + f] = s;
+            bmax = fmaxf(bmax, s);
+        }
+        __syncthreads();  // P / buffers reused by the next frame
+    }
+    // staged [n_mels][nf] tile -> melS[w][m][f0 .. f0 + nf)
+    const float inv_nm = 1.0f / (float)n_mels;  // exact row below 2^21 (as in fe_db)
+    for (int idx = tid; idx < nf * n_mels; idx += NT) {  // frame-major rows
+        const int f = (int)(((float)idx + 0.5f) * inv_nm), m = idx - f * n_mels;
+        melS[((size_t)w * T + f0 + f) * n_mels + m] = melT[m * kFpb + f];
+    }
+    // item max -> blkmax[w][fb]
+    __shared__ float red[512 / 64];
+    bmax = wave_max(bmax);
+    if ((tid & 63) == 0) red[tid >> 6] = bmax;
+    __syncthreads();
+    if (tid == 0) {
+        for (int k = 1; k < NT / 64; ++k) bmax = fmaxf(bmax, red[k]);
+        blkmax[w * nblk + fb] = bmax;
+    }
     }  // item loop
 }
 

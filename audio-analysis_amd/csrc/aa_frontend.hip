@@ -17,7 +17,8 @@
 //               on the sparse mel filterbank (CSR rows, contiguous bins).
 //   fe_db       per-window max -> power_to_db, clamp, mean_sub, layout/channels.
 // The plan is made on the host (aa_fe_plan.h); the stft kernels live in
-// aa_fe_stft.h (fe_stft_mel, fe_stft_mel_small) and aa_fe_wave4096.h.
+// aa_fe_stft.h (fe_stft_mel, fe_stft_mel_small, and fe_stft_mel_mixed for the
+// n_fft that are not powers of two) and aa_fe_wave4096.h.
 #include "aa_fe_wave4096.h"
 
 namespace aa {
@@ -229,6 +230,21 @@ static int launch_stft(const FePlan& p, const float* pcm, const aa_window* wins,
                                p.cfg.n_mels, p.kmin, p.kmax, p.cfg.normalize, p.cfg.power, p.T * n_win, melS, blkmax);
             AA_LAUNCH_CHECK();
             return AA_OK;
+        case FE_K_MIXED: {
+            // fe_stft_mel's arguments, then n_fft and the schedule, 4 bits per radix
+            unsigned sched = 0;
+            for (int i = 0; i < p.n_pass; ++i) sched |= (unsigned)p.radix[i] << (4 * i);
+            auto mixed = [&](auto kernel) -> int {
+                AA_DYN_LDS(kernel, p.lds_bytes);
+                hipLaunchKernelGGL(kernel, dim3(p.grid(n_win)), dim3(fe_mixed_threads(p.cfg.n_fft)), p.lds_bytes, st,
+                                   pcm, wins, stats, p.d_win, p.d_tw, p.d_tw2, p.d_rows, p.d_vals, p.nnz,
+                                   p.cfg.win_len, p.cfg.hop, p.T, p.cfg.n_mels, p.kmin, p.kmax, p.cfg.normalize,
+                                   p.cfg.power, p.nblk, p.nblk * n_win, melS, blkmax, p.cfg.n_fft, sched);
+                AA_LAUNCH_CHECK();
+                return AA_OK;
+            };
+            return p.tw_lds ? mixed(fe_stft_mel_mixed<PM, true>) : mixed(fe_stft_mel_mixed<PM, false>);
+        }
         case FE_K_SMALL:
             return p.cfg.n_fft == 256   ? lds(fe_stft_mel_small<256, PM>, 64 * kSmallWaves)
                    : p.cfg.n_fft == 512 ? lds(fe_stft_mel_small<512, PM>, 64 * kSmallWaves)
@@ -336,6 +352,16 @@ extern "C" int aa_fe_plan_image(const void* plan, int32_t which, void* buf, size
     return AA_OK;
 }
 
+extern "C" int aa_fe_plan_passes(const void* plan, int32_t* radices, int32_t cap, int32_t* n) {
+    const FePlan* p = static_cast<const FePlan*>(plan);
+    AA_CHECK(p && n && cap >= 0 && (radices || cap == 0), AA_ERR_INVALID, "aa_fe_plan_passes: bad argument");
+    *n = p->n_pass;
+    if (!radices) return AA_OK;  // a count query
+    AA_CHECK(cap >= p->n_pass, AA_ERR_INVALID, "aa_fe_plan_passes: room for %d radices < %d", cap, p->n_pass);
+    for (int i = 0; i < p->n_pass; ++i) radices[i] = p->radix[i];
+    return AA_OK;
+}
+
 extern "C" int aa_fe_destroy(void* plan) {
     FePlan* p = static_cast<FePlan*>(plan);
     if (!p) return AA_OK;
@@ -420,6 +446,10 @@ extern "C" int aa_fe_n_stages(const void* plan) { return plan ? FE_N_STAGES : -1
 //   stft_mel flops = T (2.5 N log2 N + N + 3 (N/2 + 1) + 2 nnz) + 5 L
 //   (real FFT as an N/2 complex FFT + split, window, |.|^p, mel rows; the
 //   normalisation pass), bytes = L f32 PCM in + n_mels T f32 mel power out.
+//   fe_stft_mel_mixed: the 2.5 N log2 N term is counted from the plan's
+//   schedule instead: per pass N/2 / r butterflies of 6 (r - 1) twiddle flops
+//   (none in pass 1) plus the radix's own adds and multiplies (2: 4, 3: 16,
+//   4: 16, 5: 44, 8: 56), and 5 N for the real split.
 extern "C" int aa_fe_stage_info(const void* plan, int32_t stage, char* name, int32_t name_len,
                                 double* flops_per_item, double* bytes_per_item) {
     const FePlan* p = static_cast<const FePlan*>(plan);
@@ -431,6 +461,15 @@ extern "C" int aa_fe_stage_info(const void* plan, int32_t stage, char* name, int
         case FE_STAGE_STATS: nm = "fe_stats"; fl = 2 * L; by = 4 * L; break;
         case FE_STAGE_STFT:
             nm = fe_kernel_name(p->kernel);
+            if (p->kernel == FE_K_MIXED) {
+                double fft = 5 * N;  // the real split
+                for (int i = 0; i < p->n_pass; ++i) {
+                    const int r = p->radix[i];
+                    const double own = r == 2 ? 4 : r == 3 ? 16 : r == 4 ? 16 : r == 5 ? 44 : 56;
+                    fft += N / 2 / r * ((i ? 6.0 * (r - 1) : 0.0) + own);
+                }
+                fl = T * (fft + N + 3 * (N / 2 + 1) + 2.0 * p->nnz) + 5 * L;
+            } else
             fl = T * (2.5 * N * std::log2(N) + N + 3 * (N / 2 + 1) + 2.0 * p->nnz) + 5 * L;
             by = 4 * L + 4 * M * T;
             break;

@@ -34,6 +34,35 @@ __device__ __forceinline__ void dft4(float2& a, float2& b, float2& c, float2& d)
     b = cadd(t1, t3);
     d = csub(t1, t3);
 }
+// in: a,b,c = x0..x2 ; out in natural order X0..X2 (W3 = -1/2 - i sin(pi/3))
+__device__ __forceinline__ void dft3(float2& a, float2& b, float2& c) {
+    const float s = (float)0.86602540378443864676;  // sin(pi/3)
+    const float2 t = cadd(b, c), d = csub(b, c);
+    const float2 u = make_float2(fmaf(-0.5f, t.x, a.x), fmaf(-0.5f, t.y, a.y));
+    const float2 v = make_float2(s * d.y, -s * d.x);  // -i s (b - c)
+    a = cadd(a, t);
+    b = cadd(u, v);
+    c = csub(u, v);
+}
+// in: v[0..4] = x0..x4 ; out in natural order X0..X4 (W5^k = cos(2 pi k/5) - i sin(2 pi k/5))
+__device__ __forceinline__ void dft5(float2* v) {
+    const float c1 = (float)0.30901699437494742410;   // cos(2 pi / 5)
+    const float c2 = (float)-0.80901699437494742410;  // cos(4 pi / 5)
+    const float s1 = (float)0.95105651629515357212;   // sin(2 pi / 5)
+    const float s2 = (float)0.58778525229247312917;   // sin(4 pi / 5)
+    const float2 a = v[0];
+    const float2 t1 = cadd(v[1], v[4]), t2 = cadd(v[2], v[3]), t3 = csub(v[1], v[4]), t4 = csub(v[2], v[3]);
+    const float2 m1 = make_float2(fmaf(c2, t2.x, fmaf(c1, t1.x, a.x)), fmaf(c2, t2.y, fmaf(c1, t1.y, a.y)));
+    const float2 m2 = make_float2(fmaf(c1, t2.x, fmaf(c2, t1.x, a.x)), fmaf(c1, t2.y, fmaf(c2, t1.y, a.y)));
+    // -i (s1 t3 + s2 t4) and -i (s2 t3 - s1 t4)
+    const float2 n1 = mul_negi(make_float2(fmaf(s2, t4.x, s1 * t3.x), fmaf(s2, t4.y, s1 * t3.y)));
+    const float2 n2 = mul_negi(make_float2(fmaf(-s1, t4.x, s2 * t3.x), fmaf(-s1, t4.y, s2 * t3.y)));
+    v[0] = cadd(a, cadd(t1, t2));
+    v[1] = cadd(m1, n1);
+    v[4] = csub(m1, n1);
+    v[2] = cadd(m2, n2);
+    v[3] = csub(m2, n2);
+}
 __device__ __forceinline__ void dft8(float2* v) {
     const float r = 0.70710678118654752440f;
     float2 e0 = v[0], e1 = v[2], e2 = v[4], e3 = v[6];

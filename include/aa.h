@@ -69,7 +69,8 @@ typedef struct aa_window {
  * src/identify_tracks.py:466-497). */
 typedef struct aa_fe_config {
     int32_t win_len;   /* samples per window: int(sr * segment_length) */
-    int32_t n_fft;     /* power of two, 256..8192 */
+    int32_t n_fft;     /* 256..8192: a power of two, or a multiple of 16 whose
+                        * sixteenth has only the factors 2, 3, 5 (4800, 1200) */
     int32_t hop;       /* hop_length */
     int32_t n_mels;    /* rows of the filterbank */
     int32_t normalize; /* normalize_data before the STFT */
@@ -93,9 +94,12 @@ const char* aa_last_error(void);
 /* ---------------- front end: PCM windows -> log-mel ---------------- */
 /* melfb: host float32 [n_mels][n_fft/2 + 1] dense filterbank (custommel.mel_f
  * or the Slaney filterbank); stored on the device in CSR form.
- * cfg->n_fft: 256, 512, 1024, 2048, 4096 or 8192; any other value is
- * AA_ERR_UNSUPPORTED before any device call.  256..1024 take any hop; from
- * 2048 up a hop whose six-frame span does not fit the LDS is refused. */
+ * cfg->n_fft: 256 <= n_fft <= 8192 and either a power of two (256, 512, 1024,
+ * 2048, 4096, 8192) or a multiple of 16 with n_fft / 16 = 2^a 3^b 5^c (400,
+ * 960, 1200, 1920, 2400, 4800, 7776, ...); any other value (odd sizes, a
+ * factor 7 or larger, 8 mod 16 such as 1000) is AA_ERR_UNSUPPORTED before any
+ * device call.  The powers of two 256..1024 take any hop; every other size
+ * refuses a hop whose six-frame span does not fit the LDS. */
 int aa_fe_create(const aa_fe_config* cfg, const float* melfb, void** plan);
 int aa_fe_destroy(void* plan);
 /* frames per window T = 1 + win_len / hop */
@@ -113,7 +117,10 @@ int aa_fe_run(void* plan, const float* pcm, int64_t pcm_len, const aa_window* wi
  * stft + mel kernel the plan chose (csrc/aa_fe_plan.h choose_kernel; its name
  * is stage_info's): fe_stft_mel_small at n_fft 256..1024, fe_stft_mel from
  * 2048 up (both csrc/aa_fe_stft.h), fe_stft_mel_4096 at n_fft 4096 with the
- * kept band inside X[2..1022] (csrc/aa_fe_wave4096.h). */
+ * kept band inside X[2..1022] (csrc/aa_fe_wave4096.h), fe_stft_mel_mixed at
+ * every n_fft that is not a power of two (csrc/aa_fe_stft.h too: Stockham passes
+ * of radix 8, 5, 4, 3, 2 by the plan's schedule, aa_fe_plan_passes; its flops
+ * per item are counted from that schedule). */
 int aa_fe_n_stages(const void* plan);
 int aa_fe_stage_info(const void* plan, int32_t stage, char* name, int32_t name_len,
                      double* flops_per_item, double* bytes_per_item);
@@ -125,7 +132,9 @@ int aa_fe_stage_time(void* plan, int32_t stage, double* total_ms, int64_t* count
  * memory and no HIP call.  aa_fe_n_frames / workspace_bytes / n_stages /
  * stage_info / destroy serve a planned plan; aa_fe_run, aa_fe_set_timing and
  * aa_fe_stage_time return AA_ERR_INVALID. */
-typedef enum aa_fe_kernel { AA_FE_K_SMALL = 0, AA_FE_K_WAVE4096 = 1, AA_FE_K_GENERIC = 2 } aa_fe_kernel;
+typedef enum aa_fe_kernel {
+    AA_FE_K_SMALL = 0, AA_FE_K_WAVE4096 = 1, AA_FE_K_GENERIC = 2, AA_FE_K_MIXED = 3
+} aa_fe_kernel;
 typedef struct aa_fe_info {
     int32_t kernel;    /* aa_fe_kernel: the stft launch (stage 1) */
     int32_t T;         /* frames per window */
@@ -146,6 +155,15 @@ int aa_fe_plan_info(const void* plan, int32_t n_win, aa_fe_info* out);
  * CSR rows int32x4 [n_mels] (first bin, count, value offset, 0), 4 the CSR
  * values f32, 5 fe_stft_mel_4096's image (len 0 unless n_fft is 4096). */
 int aa_fe_plan_image(const void* plan, int32_t which, void* buf, size_t cap, size_t* len);
+/* The Stockham passes of the plan's n_fft/2-point complex transform, planned or
+ * created: *n radices whose product is n_fft/2, written to radices[0 .. *n)
+ * (at most 8; AA_ERR_INVALID with *n set when cap < *n; radices NULL with
+ * cap 0: a count query).  AA_FE_K_MIXED runs exactly this schedule: 8 first
+ * (from the samples), then every further 8, the 5s, one 4, the 3s, one 2, each
+ * in {2, 3, 4, 5, 8}.  The other kernels report the passes built into them
+ * (8, 8, 8, 4 at 4096 AA_FE_K_GENERIC; AA_FE_K_WAVE4096's register DFT-32s as
+ * 8, 4 each: 8, 4, 8, 4, 2). */
+int aa_fe_plan_passes(const void* plan, int32_t* radices, int32_t cap, int32_t* n);
 
 /* ---------------- CNN: log-mel windows -> logits / probabilities ---------------- */
 /* Supported layer sequences: [MagTransform] then Conv2D blocks (Conv2D
